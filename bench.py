@@ -17,7 +17,15 @@ RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set, before anything touches a GPU, and
 exits with their status (rank 0 prints the line). Every rank needs its own
 GPU: ranks that would share one are refused unless --allow-shared-gpu.
 
-Also reported (rank 0):
+A plain run sets up, warms up (--warmup steps), times --repeats windows of
+exactly --steps steps each (value is the median window's rate, ms_per_step
+that window's time / --steps; once the windows have taken 10 s no further one
+is opened), writes the last timed step's outputs if --dump-outputs DIR is
+given (seeds are fixed: the same arguments give the same inputs in every
+run), and prints the line with the timed window's roofline. Everything else
+is measured by --full runs only.
+
+With --full also reported (rank 0):
   roofline      algorithmic bytes per launch / mean kernel time (HIP events
                 on the context's stream around every launch), vs 8 TB/s;
                 box_ceiling: what the same box sustains for the same byte mix
@@ -51,6 +59,7 @@ HBM_PEAK_GBS = 8000.0     # MI355X HBM3E spec (MI355X_MICROARCH.md)
 # counter words ahead of the per-rule ones in the RCCL reduction: the
 # COP_COUNTER_SHARDS x 16 counter shards, then as many port-stat shards
 SHARD_AND_PORT_WORDS = 2 * 16 * cg.COUNTER_SHARDS
+PLAIN_WINDOWS_S = 10.0    # a plain run opens no further timed window once its windows have taken this long
 TRAFFIC_DIR = os.path.join(ROOT, "bench_traffic")   # PMC traffic summaries the line quotes (travel with the tree)
 
 S, F, L = cg.STAGE_PARSE, cg.STAGE_FW, cg.STAGE_LPM
@@ -256,6 +265,42 @@ def cpu_model() -> str:
     return "unknown"
 
 
+def dump_outputs(path, slot, B, d_res, d_fwd, d_cnt, seg):
+    """--dump-outputs: what a caller of the timed path receives for the batch
+    in ring slot `slot`, one float64 .npy per array (every value is an
+    unsigned integer below 2^32, so float64 holds it exactly): the four
+    fields of the B result records, and the ordered forward list with its
+    counts (per 256-packet segment, or one per batch). List entries past a
+    count are not output (the kernel never writes them): stored as -1."""
+    os.makedirs(path, exist_ok=True)
+    rec = d_res.download(cg.RESULT_DT, B, slot * B * 8)
+    out = {f: rec[f] for f in rec.dtype.names}
+    if d_fwd is not None:
+        per = (B + cg.SEG_PKTS - 1) // cg.SEG_PKTS if seg else 1
+        cnt = d_cnt.download(np.uint32, per, slot * per * 4)
+        fwd = d_fwd.download(np.uint32, B, slot * B * 4).astype(np.float64)
+        width = cg.SEG_PKTS if seg else B
+        fwd[np.arange(B) % width >= np.repeat(cnt, width)[:B]] = -1.0
+        out["fwd_idx"], out["fwd_count"] = fwd, cnt
+    for k, a in out.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.asarray(a, dtype=np.float64))
+    log(f"[bench] outputs of the last timed step (ring slot {slot}) written to {path}: {sorted(out)}")
+
+
+def timed_roofline(res, world):
+    """A plain run's roofline: the algorithmic bytes of the timed window over
+    its time, per GPU, against the HBM peak (roofline_block's frac_timed;
+    the kernel-time, traffic and probe figures take runs of their own:
+    --full)."""
+    bpp = res.get("bytes_per_pkt")
+    if bpp is None:
+        return None
+    achieved = bpp * res["total_pkts"] / res["elapsed"] / 1e9 / world
+    return {"engine": res["engine"], "bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+            "unit": "GB/s", "frac_timed": round(achieved / HBM_PEAK_GBS, 4),
+            "algorithmic_bytes_per_pkt": round(bpp, 3)}
+
+
 def measure(args, name, rank, world, dev, group, gate, primary):
     """Time `args.steps` steps of workload `name` (+ its kernel roofline);
     returns (result dict, context). The caller closes the context. Every
@@ -423,6 +468,10 @@ def measure(args, name, rank, world, dev, group, gate, primary):
         own_runs.append((t1 - t0) * 1e-9)
         windows.append((t0, t1))
         runs.append(group.max((t1 - t0) * 1e-9))
+        if not args.full and sum(runs) + runs[-1] > PLAIN_WINDOWS_S:
+            # a plain run with very many steps: no further window (the
+            # max over ranks decides, so every rank stops at the same one)
+            break
     elapsed = float(np.median(runs))
     total_pkts = world * args.steps * B
     value = total_pkts / elapsed / 1e6
@@ -441,6 +490,26 @@ def measure(args, name, rank, world, dev, group, gate, primary):
            "bufs": (d_pkts, d_res, d_fwd, d_cnt), "ring": ring, "per_batch": per_batch}
     if W["imix"]:
         res["slab"], res["offs"] = slab, offs
+    res["total_pkts"] = total_pkts
+
+    if primary and args.dump_outputs and rank == 0:
+        # what the last timed step left in its ring slot (batch b sits in
+        # slot b % P), read once the engine is idle
+        last = (pmd.posted if pmd is not None else args.warmup + len(runs) * args.steps) - 1
+        pmd_off()
+        ctx.sync()
+        dump_outputs(args.dump_outputs, last % P, B, d_res, None if args.no_compact else d_fwd, d_cnt, seg)
+
+    if not args.full:
+        # a plain run ends here: the bytes per packet of the timed window's
+        # roofline from the counters the steps themselves left
+        pmd_off()
+        ctx.sync()
+        cnt = ctx.counters()
+        if cnt["rx"] > 0:
+            res["bytes_per_pkt"] = ((76 if W["imix"] else 72) + 4 * cnt["forward"] / cnt["rx"]
+                                    + 4.0 * cnt_per_slot / B)
+        return res, ctx
 
     # ---- the poll-mode kernel's steady state and single-batch latency ----
     if engine == "pmd" and primary and not args.quick:
@@ -832,6 +901,14 @@ def main():
                     help="test the launch and rank protocol only: no GPU, fake timings (CPU tests)")
     ap.add_argument("--dry-run-devices", type=int, default=8, help="GPUs a --dry-run pretends to see")
     ap.add_argument("--dry-run-fail-rank", type=int, default=-1, help="--dry-run: this rank exits 3 at start")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the kernel roofline, PMC traffic and table probes, "
+                         "the box's ceilings, the poll-mode steady state and latencies, the RCCL counter check, the "
+                         "secondary workloads, the CPU baselines and the end-to-end leg (a plain run sets up, warms "
+                         "up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (its batch's result records, "
+                         "ordered forward list and counts) as DIR/<name>.npy in float64 (rank 0)")
     ap.add_argument("--steps", type=int, default=16384)
     ap.add_argument("--warmup", type=int, default=2048)
     ap.add_argument("--workload", default="fw1k", choices=sorted(WORKLOADS))
@@ -877,7 +954,7 @@ def main():
     ap.add_argument("--no-numa-bind", action="store_true",
                     help="do not move the process onto the CPUs of the GPU's NUMA node")
     ap.add_argument("--quick", action="store_true",
-                    help="A/B runs: the timed steps and the kernel roofline only (no poll-mode extras, single-batch "
+                    help="--full A/B runs: the timed steps and the kernel roofline only (no poll-mode extras, single-batch "
                          "latency, ceilings, RCCL check, secondary workload or CPU baseline)")
     ap.add_argument("--no-rule-counters", action="store_true", help="ablation: config 5 without per-rule counters")
     ap.add_argument("--no-rccl-check", action="store_true",
@@ -896,10 +973,14 @@ def main():
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))
     rank, world, local = copdist.env()
+    if not args.full:
+        args.quick = True   # and measure() stops after the timed steps
     secondary = args.secondary
     if secondary == "auto":
         secondary = "fw_lpm,fw_lpm_imix,fw_lpm_1m" if args.workload == "fw1k" and not args.quick else "none"
     secondaries = [x for x in secondary.split(",") if x and x != "none" and x != args.workload]
+    if secondaries and not args.full:
+        raise SystemExit("[bench] --secondary workloads are timed by --full runs only")
     bad = [x for x in secondaries if x not in WORKLOADS]
     if bad:
         raise SystemExit(f"[bench] unknown --secondary workload(s) {bad}: choose from {sorted(WORKLOADS)}")
@@ -929,14 +1010,16 @@ def main():
     # else in flight; kernel time from HIP events, submit->sync on the host ----
     n_lat = 0 if args.quick else 50
     host_us = [0.0]
-    ctx.launch_timing(True)
-    for i in range(n_lat):
-        h0 = time.perf_counter()
-        ctx.submit_ring(res["ring"], i % P, 1)
-        ctx.sync()
-        host_us.append((time.perf_counter() - h0) * 1e6)
-    lat_ms, _ = ctx.launch_timing_read(reset=True)
-    ctx.launch_timing(False)
+    lat_ms = 0.0
+    if args.full:
+        ctx.launch_timing(True)
+        for i in range(n_lat):
+            h0 = time.perf_counter()
+            ctx.submit_ring(res["ring"], i % P, 1)
+            ctx.sync()
+            host_us.append((time.perf_counter() - h0) * 1e6)
+        lat_ms, _ = ctx.launch_timing_read(reset=True)
+        ctx.launch_timing(False)
     single_batch = None if args.quick else {"batch": B, "launches": n_lat, "kernel_us_mean": round(lat_ms * 1e3, 2),
                     "host_submit_to_sync_us_median": round(float(np.median(host_us)), 2)}
 
@@ -969,8 +1052,11 @@ def main():
     # the roofline of the engine behind `value` (config.engine), and the
     # one-shot kernel's beside it (its HIP-event launch time is what rocprofv3
     # --kernel-trace --stats of this command reports)
-    roof = roofline_block(res, world, group, args)
-    roof_launch = roof if res["engine"] != "pmd" else roofline_launch_block(res, world, group, args)
+    if args.full:
+        roof = roofline_block(res, world, group, args)
+        roof_launch = roof if res["engine"] != "pmd" else roofline_launch_block(res, world, group, args)
+    else:
+        roof = roof_launch = timed_roofline(res, world)
     if ceiling is not None:
         roof_launch["box_ceiling"] = {
             "what": "same pool, same process: read each 64 B slot + write an 8 B record, no classification "

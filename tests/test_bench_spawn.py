@@ -24,7 +24,8 @@ def json_lines(out):
 
 
 def test_spawn_two_ranks_one_line():
-    r = run("--gpus", "2", "--dry-run", "--steps", "20", "--warmup", "5", "--repeats", "3", "--cpu-budget", "0.3")
+    r = run("--gpus", "2", "--dry-run", "--full", "--steps", "20", "--warmup", "5", "--repeats", "3",
+            "--cpu-budget", "0.3")
     assert r.returncode == 0, r.stderr
     lines = json_lines(r.stdout)
     assert len(lines) == 1, r.stdout          # rank 0 only
@@ -105,7 +106,7 @@ def test_eight_ranks_gate_overlap_and_config5_block():
     the union-window rate beside the max-own value; the configs[4] secondary
     (fw_lpm_1m: 1M + 1M, 256k batches, per-rule counters reduced over all
     ranks) rides the line with its reduction checked across 8 ranks."""
-    r = run("--gpus", "8", "--dry-run", "--steps", "20", "--warmup", "5", "--repeats", "5", "--no-cpu",
+    r = run("--gpus", "8", "--dry-run", "--full", "--steps", "20", "--warmup", "5", "--repeats", "5", "--no-cpu",
             timeout=600)
     assert r.returncode == 0, r.stderr
     lines = json_lines(r.stdout)

@@ -38,6 +38,50 @@ def check_slot(res, fwd, cnt, s, B, ro, fo, what):
     assert np.array_equal(got, fo), f"{what}: slot {s} forward list"
 
 
+@pytest.mark.parametrize("steps,warmup,engine", [(20, 5, "pmd"), (1024, 3, "launch")])
+def test_plain_bench_dump_is_the_last_steps_output(tmp_path, steps, warmup, engine):
+    """A plain bench.py run (both engines of --engine auto) over a small pool
+    (8 batches, so the ring wraps) with --dump-outputs: the line carries
+    ms_per_step for exactly --steps steps per window, and the dumped arrays
+    are the oracle's records, segmented forward list and counts of the batch
+    in the last timed step's ring slot (batch b sits in slot b % P; the pool
+    is bench.py's first trace chunk, seed 0x5EED0002)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    d = str(tmp_path / "dump")
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                        "--warmup", str(warmup), "--pool-mib", "32", "--dump-outputs", d],
+                       capture_output=True, text=True, timeout=110, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    j = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][0])
+    assert j["config"]["engine"] == engine and j["steps"] == steps and j["dtype"] == "u32"
+    assert "secondary" not in j and "pmd" not in j and "roofline_launch" not in j and j["cpu_baseline"] is None
+    # (runs_ms is rounded to 0.1 us: up to 1 % of a 20-step window)
+    assert j["ms_per_step"] == pytest.approx(np.median(j["runs_ms"]) / steps, rel=1e-2)
+    assert j["value"] == pytest.approx(65536 / (np.median(j["runs_ms"]) / steps * 1e-3) / 1e6, rel=2e-2)
+    W = bench_workload("fw1k")
+    B, cid, P = W["batch"], W["cid"], j["config"]["pool_batches"]
+    assert P == 8
+    slot = (warmup + len(j["runs_ms"]) * steps - 1) % P
+    fw_rules = cg.gen_rules(0x5EED1000 + cid, W["fw"], cg.GEN_FW, 20)
+    pk = cg.gen_trace(copdist.shard_seed(0x5EED0000 + cid, 0, 0), P * B, fw_rules, None)
+    ofw = orc.OracleLpm(1024, 24)
+    ofw.setup(fw_rules["ip"], fw_rules["depth"], fw_rules["next_hop"])
+    ro, fo, _ = orc.process(pk[slot * B * 64:(slot + 1) * B * 64], B, stages=W["stages"], fw=ofw)
+    got = {f[:-4]: np.load(os.path.join(d, f)) for f in os.listdir(d)}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    for f in ro.dtype.names:
+        assert np.array_equal(got[f], ro[f].astype(np.float64)), f
+    cnt = got["fwd_count"].astype(np.uint32)
+    assert len(cnt) == nseg(B) and int(cnt.sum()) == int((got["fwd_idx"] >= 0).sum()) == len(fo)
+    assert np.array_equal(seg_to_dense(got["fwd_idx"], cnt, B), fo.astype(np.float64))
+
+
 def test_config5_poll_mode_ext_kernel_at_bench_size(gpu_ctx_factory):
     """BASELINE configs[4] exactly as bench.py times it: 1M firewall rules
     and 1M route prefixes (seeds 0x5EED1005 / 0x5EED2005), both DIR-24-8,

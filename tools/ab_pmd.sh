@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of poll-mode variants on the driver's command plus the poll-mode
-# steady state (bench.py without --quick, no CPU baseline, no secondary):
+# steady state (bench.py --full without --quick, no CPU baseline, no secondary):
 # usage: tools/ab_pmd.sh <outdir> "NAME:ENV=V ENV2=V" ...
 set -o pipefail
 out=$1; shift
@@ -8,7 +8,7 @@ mkdir -p "$out"
 for v in "$@"; do
     name=${v%%:*}; envs=${v#*:}
     [ "$envs" = "$name" ] && envs=""
-    env $envs timeout -k 10 300 python3 bench.py --steps 20 --warmup 5 --repeats 11 --no-cpu --secondary none \
+    env $envs timeout -k 10 300 python3 bench.py --full --steps 20 --warmup 5 --repeats 11 --no-cpu --secondary none \
         > "$out/$name.log" 2>&1 || exit 1
     python3 - "$out/$name.log" "$name" <<'PY'
 import json, sys

@@ -9,8 +9,8 @@
 #   pytest          every -m gpu test (one process)
 #   pytest:<expr>   the -m gpu tests matching -k <expr>
 #   smoke           __graft_entry__.smoke()
-#   bench20         the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench_default   bench.py with no flags
+#   bench20         the driver's command with every block: bench.py --full --gpus 1 --steps 20 --warmup 5
+#   bench_default   bench.py --full with no other flags
 #   slots           the driver's command at --slots static / reuse / always (quick, 11 runs each)
 #   stats20         rocprofv3 --kernel-trace --stats of the driver's command
 #   pmc_pmd         FETCH_SIZE / WRITE_SIZE passes over a 1024-batch poll-mode post + membench calibration
@@ -28,7 +28,7 @@ mkdir -p "$out"
 export TMPDIR=/tmp
 step() { "$R/tools/gpu_step.sh" "$@" || exit 99; }
 line() { grep -h '^{"metric"' "$@" | cut -c1-400; }
-B="python3 -u $R/bench.py"
+B="python3 -u $R/bench.py --full"
 for s in "$@"; do
   case $s in
     pytest)
@@ -52,7 +52,7 @@ for s in "$@"; do
         echo "$v $(line "$out/slots_$v.log" | cut -c1-200)"
       done ;;
     stats20)
-      step 300 "$out/stats20.log" rocprofv3 --kernel-trace --stats -d "$out/stats20" -o bench --output-format csv -- python3 "$R/bench.py" --steps 20 --warmup 5 --no-cpu $BENCH_ARGS ;;
+      step 300 "$out/stats20.log" rocprofv3 --kernel-trace --stats -d "$out/stats20" -o bench --output-format csv -- python3 "$R/bench.py" --full --steps 20 --warmup 5 --no-cpu $BENCH_ARGS ;;
     pmc_pmd)
       step 200 "$out/pmd_pmc_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/pmd_fetch" -o pmd --output-format csv -- python3 "$R/tools/pmc_pmd.py" run --batches 1024
       step 200 "$out/pmd_pmc_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/pmd_write" -o pmd --output-format csv -- python3 "$R/tools/pmc_pmd.py" run --batches 1024
@@ -68,8 +68,8 @@ for s in "$@"; do
         w=${wk%%:*}; k=${wk##*:}
         step 300 "$out/pmd_${w}_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/pmd_${w}_fetch" -o pmd --output-format csv -- python3 "$R/tools/pmc_pmd.py" run --workload "$w" --batches "$k"
         step 300 "$out/pmd_${w}_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/pmd_${w}_write" -o pmd --output-format csv -- python3 "$R/tools/pmc_pmd.py" run --workload "$w" --batches "$k"
-        step 400 "$out/os_${w}_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/os_${w}_fetch" -o os --output-format csv -- python3 "$R/bench.py" --quick --workload "$w" --steps 20 --warmup 5 --secondary none --no-cpu
-        step 400 "$out/os_${w}_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/os_${w}_write" -o os --output-format csv -- python3 "$R/bench.py" --quick --workload "$w" --steps 20 --warmup 5 --secondary none --no-cpu
+        step 400 "$out/os_${w}_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/os_${w}_fetch" -o os --output-format csv -- python3 "$R/bench.py" --full --quick --workload "$w" --steps 20 --warmup 5 --secondary none --no-cpu
+        step 400 "$out/os_${w}_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/os_${w}_write" -o os --output-format csv -- python3 "$R/bench.py" --full --quick --workload "$w" --steps 20 --warmup 5 --secondary none --no-cpu
       done
       step 200 "$out/mb_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/mb_fetch" -o mb --output-format csv -- "$R/tools/membench"
       step 200 "$out/mb_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/mb_write" -o mb --output-format csv -- "$R/tools/membench" ;;
@@ -83,8 +83,8 @@ for s in "$@"; do
     pmc_oneshot)
       # the one-shot kernel's PMC passes over the driver's command (reduce
       # here with tools/pmc_traffic.py and the membench passes of pmc_pmd)
-      step 300 "$out/os_pmc_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/os_fetch" -o os --output-format csv -- python3 "$R/bench.py" --quick --steps 20 --warmup 5 --secondary none --no-cpu
-      step 300 "$out/os_pmc_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/os_write" -o os --output-format csv -- python3 "$R/bench.py" --quick --steps 20 --warmup 5 --secondary none --no-cpu ;;
+      step 300 "$out/os_pmc_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/os_fetch" -o os --output-format csv -- python3 "$R/bench.py" --full --quick --steps 20 --warmup 5 --secondary none --no-cpu
+      step 300 "$out/os_pmc_write.log" rocprofv3 --pmc WRITE_SIZE -d "$out/os_write" -o os --output-format csv -- python3 "$R/bench.py" --full --quick --steps 20 --warmup 5 --secondary none --no-cpu ;;
     n2)
       # two ranks sharing the one GPU (one-shot launches: two persistent
       # kernels cannot both hold every CU), through the start gate; config

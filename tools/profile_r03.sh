@@ -14,7 +14,7 @@ out=$R/gpurun_out/p3_$wl
 mkdir -p "$out"
 export TMPDIR=/tmp
 step() { "$R/tools/gpu_step.sh" "$@" || exit 99; }
-B="$R/bench.py --quick --workload $wl"
+B="$R/bench.py --full --quick --workload $wl"
 step 400 "$out/stats.log" rocprofv3 --kernel-trace --stats -d "$out/stats" -o bench --output-format csv -- python3 $B --steps 20 --warmup 5 "$@"
 L="--engine launch --steps 2048 --warmup 0 --repeats 1"
 step 400 "$out/pmc_fetch.log" rocprofv3 --pmc FETCH_SIZE -d "$out/fetch" -o bench --output-format csv -- python3 $B $L "$@"
