@@ -27,6 +27,7 @@ CFG_FW_FORCE_DIR24, CFG_LPM_FORCE_DIR24, CFG_NO_COMPACT, CFG_RULE_COUNTERS = 0x1
 CFG_DEMUX_PORTS, CFG_PORT_STATS, CFG_LPM_TRIE, CFG_SEG_LISTS = 0x10, 0x20, 0x40, 0x80
 CFG_LPM_BKT = 0x100
 CFG_FW_BKT = 0x200
+CFG_LIVE_TABLES = 0x400   # the stage tables accept update_* patches (cop_update_*)
 SEG_PKTS = 256   # COP_SEG_PKTS: packets per forward-list segment (CFG_SEG_LISTS)
 MAX_DEMUX_PORTS = 8
 GEN_FW, GEN_ROUTES = 0, 1
@@ -58,6 +59,18 @@ class LpmReport(Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class UpdateReport(Structure):
+    _fields_ = [("full", c_uint32), ("n_changes", c_uint32), ("n_records", c_uint32),
+                ("tbl24_entries", c_uint32), ("tbl8_entries", c_uint32), ("groups_taken", c_uint32),
+                ("groups_released", c_uint32), ("h2d_bytes", c_uint64)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+PATCH_REC_DT = np.dtype([("table", "<u4"), ("first", "<u4"), ("count", "<u4"), ("entry", "<u4")])
 
 
 class Config(Structure):
@@ -112,6 +125,16 @@ SIGNATURES = {
     "cop_lpm_export_intervals": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
     "cop_lpm_export_rules": (c_int, [c_void_p, c_void_p, c_uint32]),
     "cop_lpm_lookup_rules": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    "cop_lpm_create": (c_int, [POINTER(LpmConfig), POINTER(c_void_p)]),
+    "cop_lpm_add": (c_int, [c_void_p, c_uint32, c_uint8, c_uint32]),
+    "cop_lpm_delete": (c_int, [c_void_p, c_uint32, c_uint8]),
+    "cop_lpm_delete_all": (c_int, [c_void_p]),
+    "cop_lpm_is_rule_present": (c_int, [c_void_p, c_uint32, c_uint8, POINTER(c_uint32)]),
+    "cop_lpm_generation": (c_uint64, [c_void_p]),
+    "cop_lpm_export_rules_ids": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32]),
+    "cop_update_fw_table": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
+    "cop_update_route_lpm": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
+    "cop_update_fw_rules_file": (c_int, [c_void_p, c_void_p, c_char_p, POINTER(UpdateReport)]),
     "cop_rules_load_json": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
     "cop_rules_free": (None, [c_void_p]),
     "cop_rules_write_json": (c_int, [c_char_p, c_void_p, c_uint32]),
@@ -372,6 +395,78 @@ class LpmTable:
             lib().cop_lpm_free(self.handle)
             self.handle = c_void_p()
 
+    @classmethod
+    def empty(cls, max_rules=1024, number_tbl8s=24) -> "LpmTable":
+        """An empty table (cop_lpm_create) to fill with add()."""
+        t = cls.__new__(cls)
+        cfg = LpmConfig(max_rules, number_tbl8s, 0)
+        t.handle = c_void_p()
+        t.report = LpmReport()
+        _check(lib().cop_lpm_create(byref(cfg), byref(t.handle)), what="cop_lpm_create")
+        t._refresh()
+        return t
+
+    def _refresh(self):
+        """self.report as the table is now (n_distinct, tbl8_used, n_intervals)."""
+        f = lib().cop_lpm_report_get
+        f.restype = None
+        f.argtypes = [c_void_p, POINTER(LpmReport)]
+        f(self.handle, byref(self.report))
+
+    def add(self, ip: int, depth: int, next_hop: int) -> int:
+        """rte_lpm_add: 0, or -EINVAL / -ENOSPC with the table unchanged."""
+        if not 0 <= depth <= 255:
+            return -22
+        rc = lib().cop_lpm_add(self.handle, ip & 0xFFFFFFFF, depth, next_hop & 0xFFFFFFFF)
+        self._refresh()
+        return rc
+
+    def delete(self, ip: int, depth: int) -> int:
+        """rte_lpm_delete: 0, or -EINVAL (bad depth, or the rule is not held)."""
+        if not 0 <= depth <= 255:
+            return -22
+        rc = lib().cop_lpm_delete(self.handle, ip & 0xFFFFFFFF, depth)
+        self._refresh()
+        return rc
+
+    def delete_all(self) -> int:
+        rc = lib().cop_lpm_delete_all(self.handle)
+        self._refresh()
+        return rc
+
+    def is_rule_present(self, ip: int, depth: int):
+        """(1, next hop), (0, None) or (-EINVAL, None)."""
+        if not 0 <= depth <= 255:
+            return -22, None
+        nh = c_uint32(0)
+        rc = lib().cop_lpm_is_rule_present(self.handle, ip & 0xFFFFFFFF, depth, byref(nh))
+        return rc, (nh.value if rc == 1 else None)
+
+    @property
+    def generation(self) -> int:
+        return int(lib().cop_lpm_generation(self.handle))
+
+    def rules_ids(self):
+        """(rules, ids): every held rule with its rule id (the index of its
+        per-rule counter), in id order."""
+        n = _check(lib().cop_lpm_export_rules_ids(self.handle, None, None, 0))
+        out = np.zeros(n, dtype=PREFIX_DT)
+        ids = np.zeros(n, dtype=np.uint32)
+        _check(lib().cop_lpm_export_rules_ids(self.handle, _ptr(out), _ptr(ids), n))
+        return out, ids
+
+    # -- patches for a device DIR-24-8 image (cop_internal.h; tests, tools) --
+    def live_image(self, form: int = 0, cap_groups: int | None = None) -> "LiveImage":
+        """The freshly painted DIR-24-8 image of a form (0: next hop, 1: rule
+        id) with room for cap_groups tbl8 groups, and its book of groups."""
+        return LiveImage(self, form, cap_groups)
+
+    def journal_set_cap(self, cap: int):
+        f = lib().cop_lpm_journal_set_cap
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_uint32]
+        _check(f(self.handle, cap), what="cop_lpm_journal_set_cap")
+
     def rules(self) -> np.ndarray:
         n = _check(lib().cop_lpm_export_rules(self.handle, None, 0))
         out = np.zeros(n, dtype=PREFIX_DT)
@@ -427,6 +522,79 @@ class LpmTable:
         t8 = np.zeros(cap, dtype=np.uint32)
         n_ext = _check(lib().cop_lpm_export_dir24(self.handle, _ptr(t24), _ptr(t8), cap))
         return t24, t8[: n_ext * 256]
+
+
+class LiveImage:
+    """Host copy of a patched DIR-24-8 image: tbl24 / tbl8 arrays, the book
+    of tbl8 groups (cop_live_img) and the table generation they hold.
+    records() returns the fill records that bring the image to the table's
+    current generation (and moves the book there); apply() is the host mirror
+    of the patch kernel."""
+
+    def __init__(self, table: LpmTable, form: int = 0, cap_groups: int | None = None):
+        L = lib()
+        self.table, self.form = table, form
+        L.cop_lpm_form_n_ext.restype = c_uint32
+        L.cop_lpm_form_n_ext.argtypes = [c_void_p, c_int]
+        n_ext = L.cop_lpm_form_n_ext(table.handle, form)
+        self.cap_groups = n_ext + 64 if cap_groups is None else cap_groups
+        self.tbl24 = np.zeros(1 << 24, dtype=np.uint32)
+        self.tbl8 = np.zeros(max(self.cap_groups, n_ext, 1) * 256, dtype=np.uint32)
+        L.cop_lpm_form_fill_dir24.restype = None
+        L.cop_lpm_form_fill_dir24.argtypes = [c_void_p, c_int, c_void_p, c_void_p]
+        L.cop_lpm_form_fill_dir24(table.handle, form, _ptr(self.tbl24), _ptr(self.tbl8))
+        L.cop_live_img_create.restype = c_void_p
+        L.cop_live_img_create.argtypes = [c_void_p, c_int, c_uint32]
+        self.handle = c_void_p(L.cop_live_img_create(table.handle, form, self.cap_groups))
+        if not self.handle.value:
+            raise CopError(-12, "cop_live_img_create")
+
+    def __del__(self):
+        if getattr(self, "handle", None) and self.handle.value:
+            f = lib().cop_live_img_free
+            f.restype = None
+            f.argtypes = [c_void_p]
+            f(self.handle)
+            self.handle = c_void_p()
+
+    def records(self):
+        """(records, report dict), or (None, -errno): -ESTALE (-116) when the
+        journal no longer reaches back, -ENOSPC (-28) when the groups ran out."""
+        f = lib().cop_lpm_patch_records
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_uint32), POINTER(UpdateReport)]
+        p, n, rep = c_void_p(), c_uint32(0), UpdateReport()
+        rc = f(self.table.handle, self.handle, byref(p), byref(n), byref(rep))
+        if rc < 0:
+            return None, rc
+        try:
+            buf = (ctypes.c_uint8 * (n.value * PATCH_REC_DT.itemsize)).from_address(p.value) if n.value else b""
+            recs = np.frombuffer(bytes(buf), dtype=PATCH_REC_DT).copy()
+        finally:
+            ctypes.CDLL(None).free(p)
+        return recs, rep.as_dict()
+
+    def apply(self, recs: np.ndarray):
+        patch_apply_host(self.tbl24, self.tbl8, recs)
+
+    def lookup(self, ips: np.ndarray) -> np.ndarray:
+        """The image's entry for each address (tbl24, then its tbl8 group)."""
+        ips = np.asarray(ips, dtype=np.uint32)
+        e = self.tbl24[ips >> 8]
+        ext = (e & 0x03000000) == 0x03000000
+        g = (e[ext] & 0x00FFFFFF).astype(np.int64)
+        e = e.copy()
+        e[ext] = self.tbl8[g * 256 + (ips[ext] & 0xFF)]
+        return e
+
+
+def patch_apply_host(tbl24: np.ndarray, tbl8: np.ndarray, recs: np.ndarray):
+    """cop_patch_apply_host: fill records into host arrays (the kernel's mirror)."""
+    recs = np.ascontiguousarray(recs, dtype=PATCH_REC_DT)
+    f = lib().cop_patch_apply_host
+    f.restype = c_int
+    f.argtypes = [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32]
+    _check(f(_ptr(tbl24), len(tbl24), _ptr(tbl8), len(tbl8), _ptr(recs), len(recs)), what="cop_patch_apply_host")
 
 
 ALLOC_UNCACHED, ALLOC_FINEGRAINED = 1, 2
@@ -563,6 +731,35 @@ class Context:
         _check(lib().cop_load_fw_rules_file(self.handle, path.encode(), byref(cfg), byref(rep)), self,
                "load_fw_rules_file")
         return rep
+
+    def _update(self, fn, what, *args) -> dict:
+        rep = UpdateReport()
+        _check(fn(self.handle, *args, byref(rep)), self, what)
+        return rep.as_dict()
+
+    def update_fw_table(self, t: LpmTable) -> dict:
+        """Bring the firewall stage to t's current rules (cop_update_fw_table):
+        stream-ordered, no sync needed; returns the update report."""
+        return self._update(lib().cop_update_fw_table, "update_fw_table", t.handle)
+
+    def update_route_lpm(self, t: LpmTable) -> dict:
+        return self._update(lib().cop_update_route_lpm, "update_route_lpm", t.handle)
+
+    def update_fw_rules_file(self, t: LpmTable, path: str) -> dict:
+        """Make t (and the firewall stage) hold what the edited rules file holds."""
+        rep = self._update(lib().cop_update_fw_rules_file, "update_fw_rules_file", t.handle, path.encode())
+        t._refresh()
+        return rep
+
+    def debug_patch(self, tbl24: DeviceBuffer, tbl8: DeviceBuffer, recs: np.ndarray) -> int:
+        """The patch kernel alone on two caller buffers (tests); returns the
+        records sent after cutting long runs."""
+        recs = np.ascontiguousarray(recs, dtype=PATCH_REC_DT)
+        f = lib().cop_debug_patch
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_uint32]
+        return _check(f(self.handle, tbl24.ptr, tbl24.nbytes // 4, tbl8.ptr, tbl8.nbytes // 4, _ptr(recs), len(recs)),
+                      self, "debug_patch")
 
     def alloc(self, nbytes, flags: int = 0) -> DeviceBuffer:
         """HBM (flags: ALLOC_UNCACHED / ALLOC_FINEGRAINED, cop_dev_alloc_ex)."""

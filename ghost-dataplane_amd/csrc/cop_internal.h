@@ -42,6 +42,16 @@ struct cop_lpm_table {
     uint32_t *rv_rule;
     uint32_t  n_ext_rule;
     cop_lpm_report report;
+    /* live tables (lpm_live.c): n_rules is the id space (highest id held so
+     * far + 1), rule_depth[id] == 0 marks an id freed by cop_lpm_delete and
+     * n_held counts the rules held. A table never deleted from has
+     * n_held == n_rules. The index behind add / delete is built at the first
+     * mutation, so a table that is only built and uploaded pays nothing. */
+    cop_lpm_config cfg;
+    uint32_t  n_held;
+    uint64_t  generation;        /* successful mutations since the build */
+    uint64_t  uid;               /* identity of this table object (never reused) */
+    struct cop_lpm_live *live;
 };
 
 #define COP_NO_RULE 0xFFFFFFFFu
@@ -106,6 +116,77 @@ uint32_t cop_lpm_bkt_lookup(const cop_lpm_bkt *t, uint32_t ip, uint32_t *rounds)
  * lookups that needed a wide-bucket round, the wide-bucket rounds} */
 int cop_lpm_bkt_probe(const cop_lpm_table *tab, int form, uint32_t xbits, const uint32_t *ips, uint32_t n,
                       uint32_t *out, uint32_t *ref, uint32_t *info);
+
+/* ---- live tables (lpm_live.c) ------------------------------------------ */
+void cop_lpm_live_free(struct cop_lpm_live *l);
+uint64_t cop_lpm_next_uid(void);
+/* Build the index behind add / delete / is_rule_present now (it is otherwise
+ * built at the first mutation): makes cop_lpm_is_rule_present O(1). */
+int cop_lpm_index(cop_lpm_table *t);
+/* The report as the table is now: n_distinct, tbl8_used and n_intervals follow
+ * every mutation; the other fields keep what cop_lpm_build counted. */
+void cop_lpm_report_get(const cop_lpm_table *t, cop_lpm_report *out);
+
+/* Device entry of a form for an interval value / a rule id. */
+static inline uint32_t cop_dir_entry(uint32_t ival)
+{
+    return (ival & COP_IV_HIT) ? (ival & ~0x02000000u) : 0u; /* nh | valid | depth<<26 */
+}
+static inline uint32_t cop_rule_entry(const cop_lpm_table *t, uint32_t rule)
+{
+    if (rule == COP_NO_RULE) return 0u;
+    return rule | COP_DIR_VALID | (t->rule_nh[rule] ? COP_RV_DROP : 0u);
+}
+
+/* One journalled mutation: the prefix whose address range changed. */
+enum { COP_CHG_ADD = 0, COP_CHG_SET = 1, COP_CHG_DEL = 2, COP_CHG_DEL_ALL = 3 };
+typedef struct {
+    uint32_t ip;     /* masked prefix (0 for DEL_ALL) */
+    uint32_t id;     /* rule id taken (ADD), kept (SET) or freed (DEL) */
+    uint8_t  depth;  /* 0 for DEL_ALL: the whole address space */
+    uint8_t  kind;   /* COP_CHG_* */
+} cop_lpm_change;
+#define COP_LPM_JOURNAL_CAP 65536u
+/* The mutations that took the table from generation `since` to now, oldest
+ * first (malloc-ed; NULL when there are none). Returns their number, or
+ * -ESTALE when `since` has fallen off the journal ("too old": the caller
+ * rebuilds from the whole table), -EINVAL, -ENOMEM. `cap` (tests) shrinks
+ * the journal: cop_lpm_journal_set_cap drops all but the newest cap entries. */
+int cop_lpm_changes_since(const cop_lpm_table *t, uint64_t since, cop_lpm_change **out);
+int cop_lpm_journal_set_cap(cop_lpm_table *t, uint32_t cap);
+
+/* A fill record of the patch kernel (cop_patch.hip): entries
+ * [first, first + count) of table (0: tbl24, 1: tbl8) become `entry`. */
+typedef struct {
+    uint32_t table, first, count, entry;
+} cop_patch_rec;
+
+/* Host-side book of one device DIR-24-8 image that accepts patches: which
+ * /24 blocks own which tbl8 group, the free groups, the capacity in groups
+ * and the table generation the image holds. Group numbers of a fresh image
+ * are cop_lpm_form_fill_dir24's (address order); after patches they are the
+ * image's own. */
+typedef struct cop_live_img cop_live_img;
+cop_live_img *cop_live_img_create(const cop_lpm_table *t, int form, uint32_t cap_groups);
+void cop_live_img_free(cop_live_img *img);
+uint64_t cop_live_img_generation(const cop_live_img *img);
+uint32_t cop_live_img_groups_used(const cop_live_img *img);
+/* The disjoint fill records that bring the image from its generation to the
+ * table's (malloc-ed; *n may be 0), and the image's book with them. rep gets
+ * n_changes, tbl24_entries, tbl8_entries, groups_taken, groups_released.
+ * 0, -ESTALE (journal too old), -ENOSPC (more groups needed than the image
+ * has), -ENOMEM. After an error the book is stale: repaint the whole image
+ * and create a new book. */
+int cop_lpm_patch_records(const cop_lpm_table *t, cop_live_img *img, cop_patch_rec **recs, uint32_t *n,
+                          cop_update_report *rep);
+/* Host mirror of the patch kernel: apply records to host arrays of cap24 /
+ * cap8 entries. -EINVAL (and nothing written) if a record leaves its array. */
+int cop_patch_apply_host(uint32_t *tbl24, uint32_t cap24, uint32_t *tbl8, uint32_t cap8, const cop_patch_rec *recs,
+                         uint32_t n);
+/* tests: the patch kernel alone, on device buffers the caller allocated
+ * (16-byte aligned, cap24 / cap8 entries); synchronous */
+int cop_debug_patch(cop_ctx *c, void *tbl24_dptr, uint32_t cap24, void *tbl8_dptr, uint32_t cap8,
+                    const cop_patch_rec *recs, uint32_t n);
 
 /* tests: the route stage's table form a launch would use (COPK_TBL_*: 1 LDS
  * intervals, 2 DIR-24-8, 3 trie, 4 bucketed) */

@@ -236,6 +236,13 @@ hipError_t copk_hit_count(const CopKParams *p, uint32_t n_tiles, uint32_t tile_p
 // dst[i] = src[i] (atomic load) or atomic exchange with 0 when reset
 hipError_t copk_snapshot(unsigned long long *src, uint32_t n_words, unsigned long long *dst, int reset,
                          hipStream_t stream);
+// cop_lpm_patch (cop_patch.hip): n disjoint fill records {table, first, count,
+// entry} (device memory, 16 bytes each, count <= COPK_PATCH_SPAN) written into
+// tbl24 (cap24 entries) and tbl8 (cap8 entries); both bases 16-byte aligned.
+// A record that leaves its table is skipped, never written in part.
+#define COPK_PATCH_SPAN 1024u
+hipError_t copk_patch_launch(const void *recs, uint32_t n, uint32_t *tbl24, uint32_t cap24, uint32_t *tbl8,
+                             uint32_t cap8, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -61,6 +61,28 @@ struct DevLpm {
     // pairs padded with COP_BKT_PADS (8) {0xFFFFFFFF, last value}; null if not built
     uint32_t *bidx = nullptr, *bpairs = nullptr;
     uint32_t b_m = 0;
+    // live tables (COP_CFG_LIVE_TABLES): the book of the patched DIR-24-8
+    // image (lpm_live.c: which /24 owns which tbl8 group, the free groups,
+    // the table generation the image holds), the table object it was made
+    // from, and the tbl8 capacity in groups; starts / vals then have room for
+    // any LDS interval image (IVT_MAX entries), whatever m is
+    cop_live_img *img = nullptr;
+    uint64_t tab_uid = 0;
+    uint32_t grp_cap = 0;
+};
+
+// cop_update_*: pinned staging for patch records and for the LDS interval
+// image, two slots used in turn; `copied` tells when the copy engine has read
+// a slot's host side
+constexpr uint32_t LIVE_STAGE_RECS = 65536;                  // 1 MiB of records per launch
+constexpr uint32_t IVT_IW_MAX = ((4096u + 2u) / 2u + 3u) & ~3u;   // index words at ib = 12
+constexpr uint32_t IVT_STAGE_WORDS = 2 * IVT_MAX + IVT_IW_MAX;
+struct LiveStage {
+    cop_patch_rec *h = nullptr;
+    void *d = nullptr;
+    uint32_t *h_ivt = nullptr;
+    hipEvent_t copied = nullptr;
+    bool used = false;
 };
 
 struct Lane {
@@ -326,6 +348,13 @@ struct cop_ctx {
         bool busy = false;
     } hs[COP_HOST_SLOTS];
     cop_pmd *pmd = nullptr;             // the poll-mode kernel serving this context, if any
+    // cop_update_* (allocated at the first update): staging, one event per
+    // lane (the patch waits for the lane's last launch) and the patch's own
+    // (every lane's next launch waits for it)
+    LiveStage live_stage[2];
+    int live_next = 0;
+    hipEvent_t live_lane_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t live_done = nullptr;
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -423,6 +452,7 @@ static void free_lpm(DevLpm &t)
     if (t.tleaves) (void)hipFree(t.tleaves);
     if (t.bidx) (void)hipFree(t.bidx);
     if (t.bpairs) (void)hipFree(t.bpairs);
+    cop_live_img_free(t.img);
     t = DevLpm();
 }
 
@@ -483,6 +513,15 @@ void cop_destroy(cop_ctx *c)
     if (c->tele_stream) (void)hipStreamDestroy(c->tele_stream);
     if (c->tele_host) (void)hipHostFree(c->tele_host);
     if (c->tele_dev) (void)hipFree(c->tele_dev);
+    for (auto &S : c->live_stage) {
+        if (S.h) (void)hipHostFree(S.h);
+        if (S.h_ivt) (void)hipHostFree(S.h_ivt);
+        if (S.d) (void)hipFree(S.d);
+        if (S.copied) (void)hipEventDestroy(S.copied);
+    }
+    for (auto &e : c->live_lane_ev)
+        if (e) (void)hipEventDestroy(e);
+    if (c->live_done) (void)hipEventDestroy(c->live_done);
     delete c->gather;
     delete c;
 }
@@ -743,6 +782,50 @@ static void pack_tbl8(std::vector<uint32_t> &h24, std::vector<uint32_t> &h8)
     h8.swap(blk);
 }
 
+// The LDS interval image of m intervals: M padded entries, ib bucket bits,
+// iw index words (its LDS footprint is 2 M + iw words).
+static void ivt_geometry(uint32_t m, uint32_t *M, uint32_t *ib_out, uint32_t *iw)
+{
+    *M = next_pow2(m < 4 ? 4 : m);
+    uint32_t ib = 0;
+    while ((1u << ib) < m && ib < 12) ib++;
+    if (ib < 6) ib = 6;
+    *ib_out = ib;
+    *iw = (((1u << ib) + 2) / 2 + 3) & ~3u;
+}
+
+// Bucketed form for LDS: the sorted starts (padded with 0xFFFFFFFF,
+// which only ip 0xFFFFFFFF reaches: its value, the last real
+// interval's, is repeated in the pads) and, per bucket of the top ib
+// bits, the position of its first candidate (R(bucket start), R(x) =
+// the last k with sorted[k] <= x); a lookup reads the bucket's two
+// index entries, then binary-lifts over at most lv levels inside the
+// bucket: 2 + lv dependent LDS reads instead of log2(M) + 1.
+// img: M starts then the iw index words; hv: M values. Returns lv.
+static uint32_t build_ivt(const uint32_t *s, const uint32_t *v, uint32_t m, uint32_t M, uint32_t ib, uint32_t iw,
+                          uint32_t *img, uint32_t *hv)
+{
+    for (uint32_t k = 0; k < M; k++) {
+        img[k] = k < m ? s[k] : 0xFFFFFFFFu;
+        hv[k] = k < m ? v[k] : v[m - 1];
+    }
+    memset(img + M, 0, (size_t)iw * 4);
+    const uint32_t nb = 1u << ib;
+    std::vector<uint16_t> idx(nb + 1);
+    uint32_t k = 0, widest = 0;
+    for (uint32_t b = 0; b <= nb; b++) {
+        // R(b << (32 - ib)); the end sentinel is R(0xFFFFFFFF) = M - 1
+        const uint64_t x = b == nb ? 0xFFFFFFFFull : (uint64_t)b << (32 - ib);
+        while (k + 1 < M && img[k + 1] <= x) k++;
+        idx[b] = (uint16_t)k;
+        if (b) widest = std::max<uint32_t>(widest, idx[b] - idx[b - 1]);
+    }
+    memcpy(img + M, idx.data(), idx.size() * sizeof(uint16_t));   // the index words (LE u16 pairs)
+    uint32_t lv = 0;
+    while ((1u << lv) <= widest) lv++;
+    return lv;
+}
+
 // the multibit-trie form of intervals (s, v, m) into t (COP_CFG_LPM_TRIE)
 static int upload_trie(cop_ctx *c, DevLpm &t, const uint32_t *s, const uint32_t *v, uint32_t m)
 {
@@ -792,46 +875,23 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
     uint32_t *s = nullptr, *v = nullptr;
     uint32_t m = cop_lpm_form_intervals(tab, form, &s, &v);
     if (!s) return set_err(c, -ENOMEM, "interval export failed");
-    if (want_ivt && m <= IVT_MAX) {
-        // Bucketed form for LDS: the sorted starts (padded with 0xFFFFFFFF,
-        // which only ip 0xFFFFFFFF reaches: its value, the last real
-        // interval's, is repeated in the pads) and, per bucket of the top ib
-        // bits, the position of its first candidate (R(bucket start), R(x) =
-        // the last k with sorted[k] <= x); a lookup reads the bucket's two
-        // index entries, then binary-lifts over at most lv levels inside the
-        // bucket: 2 + lv dependent LDS reads instead of log2(M) + 1.
-        const uint32_t M = next_pow2(m < 4 ? 4 : m);
-        std::vector<uint32_t> sorted(M), hv(M);
-        for (uint32_t k = 0; k < M; k++) {
-            sorted[k] = k < m ? s[k] : 0xFFFFFFFFu;
-            hv[k] = k < m ? v[k] : v[m - 1];
+    const bool live = (c->cfg.flags & COP_CFG_LIVE_TABLES) != 0;
+    if (want_ivt && (m <= IVT_MAX || live)) {
+        // a live context's buffers hold any LDS image a later update may bring
+        uint32_t M = 0, ib = 0, iw = 0;
+        ivt_geometry(m <= IVT_MAX ? m : IVT_MAX, &M, &ib, &iw);
+        HIPCHK(c, hipMalloc(&t.starts, (size_t)(live ? IVT_MAX + IVT_IW_MAX : M + iw) * 4));
+        HIPCHK(c, hipMalloc(&t.vals, (size_t)(live ? IVT_MAX : M) * 4));
+        if (m <= IVT_MAX) {
+            std::vector<uint32_t> img(M + iw), hv(M);
+            const uint32_t lv = build_ivt(s, v, m, M, ib, iw, img.data(), hv.data());
+            HIPCHK(c, hipMemcpy(t.starts, img.data(), (size_t)(M + iw) * 4, hipMemcpyHostToDevice));
+            HIPCHK(c, hipMemcpy(t.vals, hv.data(), M * 4, hipMemcpyHostToDevice));
+            t.m = M;
+            t.ib = ib;
+            t.lv = lv;
+            t.iw = iw;
         }
-        uint32_t ib = 0;
-        while ((1u << ib) < m && ib < 12) ib++;
-        if (ib < 6) ib = 6;
-        const uint32_t nb = 1u << ib, iw = ((nb + 2) / 2 + 3) & ~3u;
-        std::vector<uint32_t> img(M + iw, 0);
-        std::copy(sorted.begin(), sorted.end(), img.begin());
-        std::vector<uint16_t> idx(nb + 1);
-        uint32_t k = 0, widest = 0;
-        for (uint32_t b = 0; b <= nb; b++) {
-            // R(b << (32 - ib)); the end sentinel is R(0xFFFFFFFF) = M - 1
-            const uint64_t x = b == nb ? 0xFFFFFFFFull : (uint64_t)b << (32 - ib);
-            while (k + 1 < M && sorted[k + 1] <= x) k++;
-            idx[b] = (uint16_t)k;
-            if (b) widest = std::max<uint32_t>(widest, idx[b] - idx[b - 1]);
-        }
-        memcpy(img.data() + M, idx.data(), idx.size() * sizeof(uint16_t));   // the index words (LE u16 pairs)
-        uint32_t lv = 0;
-        while ((1u << lv) <= widest) lv++;
-        HIPCHK(c, hipMalloc(&t.starts, (size_t)(M + iw) * 4));
-        HIPCHK(c, hipMalloc(&t.vals, M * 4));
-        HIPCHK(c, hipMemcpy(t.starts, img.data(), (size_t)(M + iw) * 4, hipMemcpyHostToDevice));
-        HIPCHK(c, hipMemcpy(t.vals, hv.data(), M * 4, hipMemcpyHostToDevice));
-        t.m = M;
-        t.ib = ib;
-        t.lv = lv;
-        t.iw = iw;
     }
     int trc = 0;
     if (want_bkt && !t.m) trc = upload_bkt(c, t, s, v, m);     // too large for the LDS interval form
@@ -841,10 +901,19 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
     if (trc) return trc;
     // DIR-24-8 image (always: FORCE_DIR24 and the large-table path)
     const uint32_t n_ext = cop_lpm_form_n_ext(tab, form);
+    // a live image's groups are plain, with spare ones for later updates: at
+    // most twice the table's number_tbl8s (only a rule deeper than 24 puts a
+    // boundary inside a /24, and within one update a /24 may take a group
+    // before another gives its own back); when they run out the update
+    // uploads afresh
+    uint32_t grp_cap = n_ext ? n_ext : 1;
+    if (live)
+        grp_cap = (uint32_t)std::max<uint64_t>(
+            n_ext, std::min<uint64_t>(2 * (uint64_t)tab->cfg.number_tbl8s, (uint64_t)n_ext + std::max(256u, n_ext / 2)));
     std::vector<uint32_t> h24((size_t)1 << 24);
-    std::vector<uint32_t> h8((size_t)(n_ext ? n_ext : 1) * 256);
+    std::vector<uint32_t> h8((size_t)(grp_cap ? grp_cap : 1) * 256);
     cop_lpm_form_fill_dir24(tab, form, h24.data(), h8.data());
-    const bool packed = tbl8_pack_wanted(n_ext);
+    const bool packed = !live && tbl8_pack_wanted(n_ext);
     if (packed) pack_tbl8(h24, h8);
     HIPCHK(c, hipMalloc(&t.tbl24, h24.size() * 4));
     HIPCHK(c, hipMalloc(&t.tbl8, h8.size() * 4));
@@ -853,6 +922,12 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
     t.n_ext = n_ext;
     t.tbl8_packed = packed;
     t.tbl8_bytes = h8.size() * 4;
+    if (live) {
+        t.img = cop_live_img_create(tab, form, grp_cap);
+        if (!t.img) return set_err(c, -ENOMEM, "live table book");
+        t.tab_uid = tab->uid;
+        t.grp_cap = grp_cap;
+    }
     t.loaded = true;
     HIPCHK(c, hipDeviceSynchronize());   // the copies have landed before any lane reads them
     return 0;
@@ -890,7 +965,10 @@ int cop_set_fw_table(cop_ctx *c, const cop_lpm_table *t)
         (void)upload_empty_ivt(c, c->fw);
         return rc;
     }
-    if (c->cfg.flags & COP_CFG_RULE_COUNTERS) rc = resize_counters(c, t->n_rules);
+    // a live context's rule words cover every id the table can hand out
+    uint32_t n_ctr = t->n_rules;
+    if (c->cfg.flags & COP_CFG_LIVE_TABLES) n_ctr = std::max(n_ctr, std::min(t->cfg.max_rules, COP_LPM_NH_MASK + 1u));
+    if (c->cfg.flags & COP_CFG_RULE_COUNTERS) rc = resize_counters(c, n_ctr);
     return rc;
 }
 
@@ -2950,6 +3028,309 @@ int cop_pmd_stop(cop_pmd *m)
     if (c->pmd == m) c->pmd = nullptr;
     delete m;
     return rc;
+}
+
+// ---- live table updates (COP_CFG_LIVE_TABLES) ------------------------------
+// cop_update_* brings a stage's device images from the table generation the
+// context last applied to the table's current one: fill records for the
+// DIR-24-8 image (lpm_live.c), applied by cop_lpm_patch (cop_patch.hip), a
+// fresh LDS interval image when the table has one, and zeroed per-rule
+// counter words for ids that were freed. Nothing is patched while a reader
+// runs. One-shot launches: the patch is enqueued on lane 0's stream behind an
+// event of every other lane's last launch, and every other lane's stream then
+// waits for the patch's event; no host wait, no allocation. Poll-mode kernel:
+// paused (it finishes every batch below its gates and leaves), patched,
+// its stored table parameters refreshed, relaunched.
+
+static int live_setup(cop_ctx *c)
+{
+    if (c->live_done) return 0;
+    for (auto &S : c->live_stage) {
+        HIPCHK(c, hipHostMalloc(&S.h, (size_t)LIVE_STAGE_RECS * sizeof(cop_patch_rec), hipHostMallocDefault));
+        HIPCHK(c, hipHostMalloc(&S.h_ivt, (size_t)IVT_STAGE_WORDS * 4, hipHostMallocDefault));
+        HIPCHK(c, hipMalloc(&S.d, (size_t)LIVE_STAGE_RECS * sizeof(cop_patch_rec)));
+        HIPCHK(c, hipEventCreateWithFlags(&S.copied, hipEventDisableTiming));
+    }
+    for (int l = 0; l < c->n_lanes; l++)
+        HIPCHK(c, hipEventCreateWithFlags(&c->live_lane_ev[l], hipEventDisableTiming));
+    HIPCHK(c, hipEventCreateWithFlags(&c->live_done, hipEventDisableTiming));
+    return 0;
+}
+
+// the next staging slot, once the copy engine has read what it last held
+static int live_slot(cop_ctx *c, LiveStage **out)
+{
+    LiveStage &S = c->live_stage[c->live_next];
+    c->live_next ^= 1;
+    if (S.used) HIPCHK(c, hipEventSynchronize(S.copied));
+    *out = &S;
+    return 0;
+}
+
+// Records, cut into pieces of at most COPK_PATCH_SPAN entries that start on
+// a 16-byte boundary (all but a run's first), through pinned staging into the
+// patch kernel on lane 0's stream; one launch per LIVE_STAGE_RECS pieces.
+static int live_send(cop_ctx *c, const cop_patch_rec *recs, uint32_t n, uint32_t *t24, uint32_t cap24, uint32_t *t8,
+                     uint32_t cap8, cop_update_report *rep)
+{
+    uint32_t i = 0, off = 0;   // record i, its entries already cut
+    while (i < n) {
+        LiveStage *S = nullptr;
+        if (int rc = live_slot(c, &S)) return rc;
+        uint32_t k = 0;
+        while (i < n && k < LIVE_STAGE_RECS) {
+            if (recs[i].count == 0) {
+                i++;
+                continue;
+            }
+            const uint32_t first = recs[i].first + off;
+            const uint32_t cnt = std::min(recs[i].count - off, COPK_PATCH_SPAN - (first & 3u));
+            S->h[k++] = cop_patch_rec{recs[i].table, first, cnt, recs[i].entry};
+            off += cnt;
+            if (off == recs[i].count) {
+                i++;
+                off = 0;
+            }
+        }
+        if (!k) break;
+        HIPCHK(c, hipMemcpyAsync(S->d, S->h, (size_t)k * sizeof(cop_patch_rec), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipEventRecord(S->copied, c->stream));
+        S->used = true;
+        hipError_t e = copk_patch_launch(S->d, k, t24, cap24, t8, cap8, c->stream);
+        if (e != hipSuccess) return set_err(c, -EIO, "patch launch: %s", hipGetErrorString(e));
+        rep->n_records += k;
+        rep->h2d_bytes += (uint64_t)k * sizeof(cop_patch_rec);
+    }
+    return 0;
+}
+
+// the stage's LDS interval image of the table as it is now, copied in stream
+// order; later launches use the new m, ib, lv, iw
+static int live_ivt(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, int form, cop_update_report *rep)
+{
+    uint32_t *s = nullptr, *v = nullptr;
+    const uint32_t m = cop_lpm_form_intervals(tab, form, &s, &v);
+    if (!s) return set_err(c, -ENOMEM, "interval export failed");
+    uint32_t M = 0, ib = 0, iw = 0;
+    ivt_geometry(m, &M, &ib, &iw);
+    LiveStage *S = nullptr;
+    int rc = live_slot(c, &S);
+    if (!rc) {
+        const uint32_t lv = build_ivt(s, v, m, M, ib, iw, S->h_ivt, S->h_ivt + M + iw);
+        hipError_t e = hipMemcpyAsync(t.starts, S->h_ivt, (size_t)(M + iw) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(t.vals, S->h_ivt + M + iw, (size_t)M * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipEventRecord(S->copied, c->stream);
+        S->used = true;
+        if (e != hipSuccess) rc = set_err(c, -EIO, "interval image copy: %s", hipGetErrorString(e));
+        t.m = M;
+        t.ib = ib;
+        t.lv = lv;
+        t.iw = iw;
+        rep->h2d_bytes += (uint64_t)(2 * M + iw) * 4;
+    }
+    free(s);
+    free(v);
+    return rc;
+}
+
+// the device side of one update; the caller has made the GPU free of readers
+// of this stage's images in c->stream's order
+static int live_apply(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, int form, bool ivt_new, const cop_patch_rec *recs,
+                      uint32_t n, const cop_lpm_change *chg, int n_chg, cop_update_report *rep)
+{
+    if (int rc = live_send(c, recs, n, t.tbl24, 1u << 24, t.tbl8, t.grp_cap * 256u, rep)) return rc;
+    if (ivt_new) {
+        if (int rc = live_ivt(c, t, tab, form, rep)) return rc;
+    } else {
+        t.m = 0;   // past IVT_MAX: launches take the DIR-24-8 image
+    }
+    if (form == COP_FORM_RULE && c->n_rule_ctr) {
+        // ids freed since the last applied generation start from zero again
+        // (a u64 word is two entries of the patch kernel)
+        std::vector<cop_patch_rec> z;
+        bool all = false;
+        for (int i = 0; i < n_chg && !all; i++) {
+            if (chg[i].kind == COP_CHG_DEL_ALL) all = true;
+            else if (chg[i].kind == COP_CHG_DEL && chg[i].id < c->n_rule_ctr) z.push_back(cop_patch_rec{0, 2 * chg[i].id, 2, 0});
+        }
+        if (all) z.assign(1, cop_patch_rec{0, 0, 2 * c->n_rule_ctr, 0});
+        if (!z.empty())
+            if (int rc = live_send(c, z.data(), (uint32_t)z.size(), (uint32_t *)(c->counters + RULE_OFF), 2 * c->n_rule_ctr,
+                                   nullptr, 0, rep))
+                return rc;
+    }
+    t.n_ext = cop_live_img_groups_used(t.img);
+    return 0;
+}
+
+static int live_update(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_update_report *rep_out)
+{
+    if (!c || !tab) return -EINVAL;
+    DevLpm &t = is_fw ? c->fw : c->lpm;
+    const int form = is_fw ? COP_FORM_RULE : COP_FORM_NH;
+    const uint32_t fl = c->cfg.flags;
+    cop_update_report rep;
+    memset(&rep, 0, sizeof(rep));
+    if (rep_out) *rep_out = rep;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the whole-table upload instead: not a live context, another table (or
+    // none) in the stage, or a stage in the trie or a bucketed form
+    bool full = !(fl & COP_CFG_LIVE_TABLES) || !t.img || t.tab_uid != tab->uid ||
+                (fl & (is_fw ? COP_CFG_FW_BKT : (COP_CFG_LPM_TRIE | COP_CFG_LPM_BKT))) != 0;
+    const bool want_ivt = !(fl & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24));
+    const uint32_t m_new = is_fw ? tab->n_rv : tab->report.n_intervals;
+    const bool ivt_new = want_ivt && m_new <= IVT_MAX;
+    cop_patch_rec *recs = nullptr;
+    uint32_t n = 0;
+    cop_lpm_change *chg = nullptr;
+    int n_chg = 0;
+    if (c->pmd && !full) {
+        if (is_fw && (fl & COP_CFG_RULE_COUNTERS))
+            return set_err(c, -EBUSY, "per-rule counters: update the firewall table with the poll-mode kernel stopped");
+        // the kernel's launch geometry must stay: the stage's form and the
+        // LDS bytes of its interval image
+        uint32_t M = 0, ib = 0, iw = 0;
+        if (ivt_new) ivt_geometry(m_new, &M, &ib, &iw);
+        if (ivt_new != (t.m != 0) || (ivt_new && (M != t.m || iw != t.iw)))
+            return set_err(c, -EBUSY, "the update changes the poll-mode kernel's launch geometry (cop_pmd_stop first)");
+    }
+    if (!full) {
+        const uint64_t g0 = cop_live_img_generation(t.img);
+        n_chg = cop_lpm_changes_since(tab, g0, &chg);
+        int rc = n_chg < 0 ? n_chg : cop_lpm_patch_records(tab, t.img, &recs, &n, &rep);
+        if (rc == -ESTALE || rc == -ENOSPC) {
+            // the journal no longer reaches back to the image's generation, or
+            // the image is out of tbl8 groups
+            full = true;
+            if (rc == -ENOSPC) {   // the book is ahead of the image now
+                cop_live_img_free(t.img);
+                t.img = nullptr;
+            }
+        } else if (rc) {
+            free(chg);
+            return set_err(c, rc, "patch records: %d", rc);
+        }
+        rep.n_records = 0;   // counted as sent, after long runs are cut (live_send)
+    }
+    if (full) {
+        free(chg);
+        free(recs);
+        if (c->pmd)
+            return set_err(c, -EBUSY, "the update needs a whole-table upload (cop_pmd_stop first)");
+        const int rc = is_fw ? cop_set_fw_table(c, tab) : cop_set_route_lpm(c, tab);
+        if (rc) return rc;
+        memset(&rep, 0, sizeof(rep));
+        rep.full = 1;
+        rep.h2d_bytes = ((uint64_t)4 << 24) + t.tbl8_bytes + (t.m ? (uint64_t)(2 * t.m + t.iw) * 4 : 0);
+        if (rep_out) *rep_out = rep;
+        return 0;
+    }
+    int rc = live_setup(c);
+    if (!rc && c->pmd) {
+        cop_pmd *m = c->pmd;
+        if ((rc = pmd_pause(c)) == 0) {
+            rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
+            if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "patch sync");
+            // the stored launch parameters: the table fields, as fill_launch sets them
+            CopKParams &p = m->P.k;
+            p.fw_m = m->fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
+            p.fw_ib = c->fw.ib;
+            p.fw_lv = c->fw.lv;
+            p.fw_iw = m->fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
+            p.lpm_m = m->lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
+            p.lpm_ib = c->lpm.ib;
+            p.lpm_lv = c->lpm.lv;
+            p.lpm_iw = m->lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
+            const int rrc = pmd_resume(c);
+            if (!rc) rc = rrc;
+        }
+    } else if (!rc) {
+        hipError_t e = hipSuccess;
+        for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) {
+            e = hipEventRecord(c->live_lane_ev[l], c->lane[l].s);
+            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->live_lane_ev[l], 0);
+        }
+        if (e != hipSuccess) rc = set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+        if (!rc) rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
+        // every lane's next launch comes after whatever part of the patch was enqueued
+        e = hipEventRecord(c->live_done, c->stream);
+        for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) e = hipStreamWaitEvent(c->lane[l].s, c->live_done, 0);
+        if (e != hipSuccess && !rc) rc = set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+    }
+    free(chg);
+    free(recs);
+    if (rc) {
+        // the image may hold part of the update: the next update uploads afresh
+        cop_live_img_free(t.img);
+        t.img = nullptr;
+        return rc;
+    }
+    if (rep_out) *rep_out = rep;
+    return 0;
+}
+
+int cop_update_fw_table(cop_ctx *c, const cop_lpm_table *t, cop_update_report *rep)
+{
+    if (c && t && t->n_rules > COP_LPM_NH_MASK) return set_err(c, -EINVAL, "rule ids exceed 24 bits");
+    return live_update(c, true, t, rep);
+}
+
+int cop_update_route_lpm(cop_ctx *c, const cop_lpm_table *t, cop_update_report *rep)
+{
+    return live_update(c, false, t, rep);
+}
+
+int cop_update_fw_rules_file(cop_ctx *c, cop_lpm_table *t, const char *path, cop_update_report *rep)
+{
+    if (!c || !t) return -EINVAL;
+    cop_prefix *rules = nullptr;
+    uint32_t n = 0;
+    int rc = cop_rules_load_json(path, &rules, &n);
+    if (rc) return set_err(c, rc, "rules file %s: error %d", path ? path : "(null)", rc);
+    // what cop_lpm_build accepts from the file under the table's own limits
+    cop_lpm_table *want = nullptr;
+    rc = cop_lpm_build(rules, n, &t->cfg, &want, nullptr);
+    cop_rules_free(rules);
+    if (!rc) rc = cop_lpm_index(want);
+    if (rc) {
+        cop_lpm_free(want);
+        return set_err(c, rc, "lpm build failed: %d", rc);
+    }
+    // rules that left go first, so the rest fits the limits at every step
+    std::vector<cop_prefix> have(t->n_held ? t->n_held : 1), keep(want->n_held ? want->n_held : 1);
+    const int nh = cop_lpm_export_rules(t, have.data(), (uint32_t)have.size());
+    const int nk = cop_lpm_export_rules(want, keep.data(), (uint32_t)keep.size());
+    for (int i = 0; i < nh && !rc; i++)
+        if (cop_lpm_is_rule_present(want, have[i].ip, have[i].depth, nullptr) == 0)
+            rc = cop_lpm_delete(t, have[i].ip, have[i].depth);
+    for (int i = 0; i < nk && !rc; i++) {
+        uint32_t nhop = 0;
+        if (cop_lpm_is_rule_present(t, keep[i].ip, keep[i].depth, &nhop) == 1 && nhop == keep[i].next_hop) continue;
+        rc = cop_lpm_add(t, keep[i].ip, keep[i].depth, keep[i].next_hop);
+    }
+    cop_lpm_free(want);
+    if (rc) return set_err(c, rc, "rules file %s: table change failed: %d", path, rc);
+    return cop_update_fw_table(c, t, rep);
+}
+
+/* tests: the patch kernel alone on caller buffers (cop_internal.h) */
+int cop_debug_patch(cop_ctx *c, void *tbl24_dptr, uint32_t cap24, void *tbl8_dptr, uint32_t cap8,
+                    const cop_patch_rec *recs, uint32_t n)
+{
+    if (!c || (n && !recs) || (((uintptr_t)tbl24_dptr | (uintptr_t)tbl8_dptr) & 15u)) return -EINVAL;
+    for (uint32_t i = 0; i < n; i++) {
+        const uint32_t cap = recs[i].table ? cap8 : cap24;
+        if (recs[i].table > 1 || recs[i].first > cap || recs[i].count > cap - recs[i].first)
+            return set_err(c, -EINVAL, "record %u leaves its table", i);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = sync_lanes(c)) return rc;
+    if (int rc = live_setup(c)) return rc;
+    cop_update_report rep;
+    memset(&rep, 0, sizeof(rep));
+    if (int rc = live_send(c, recs, n, (uint32_t *)tbl24_dptr, cap24, (uint32_t *)tbl8_dptr, cap8, &rep)) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return (int)rep.n_records;
 }
 
 /* diagnostic (not in the public header): the poll-mode kernel's phase

@@ -155,6 +155,7 @@ void cop_lpm_free(cop_lpm_table *t)
     free(t->iv_val);
     free(t->rv_start);
     free(t->rv_rule);
+    cop_lpm_live_free(t->live);
     free(t);
 }
 
@@ -170,6 +171,8 @@ int cop_lpm_build(const cop_prefix *rules, uint32_t n, const cop_lpm_config *cfg
 
     cop_lpm_table *t = (cop_lpm_table *)calloc(1, sizeof(*t));
     if (!t) return -ENOMEM;
+    t->cfg = *cfg;   /* kept: cop_lpm_add / cop_lpm_delete (lpm_live.c) go on by the same limits */
+    t->uid = cop_lpm_next_uid();
     cop_lpm_report *rep = &t->report;
     rep->n_in = n;
 
@@ -250,6 +253,7 @@ int cop_lpm_build(const cop_prefix *rules, uint32_t n, const cop_lpm_config *cfg
     }
     umap_free(&rmap);
     umap_free(&pmap);
+    t->n_held = t->n_rules;
     rep->n_distinct = t->n_rules;
     rep->tbl8_used = t->tbl8_used;
 
@@ -488,13 +492,18 @@ int cop_lpm_export_intervals(const cop_lpm_table *t, uint32_t *starts, uint32_t 
 int cop_lpm_export_rules(const cop_lpm_table *t, cop_prefix *out, uint32_t cap)
 {
     if (!t) return -EINVAL;
-    if (!out) return (int)t->n_rules;
-    if (t->n_rules > cap) return -ENOSPC;
+    if (!out) return (int)t->n_held;
+    if (t->n_held > cap) return -ENOSPC;
+    /* ids freed by cop_lpm_delete (depth 0) are skipped; a table never
+     * deleted from has none, and the position is the rule id */
+    uint32_t k = 0;
     for (uint32_t i = 0; i < t->n_rules; i++) {
-        memset(&out[i], 0, sizeof(out[i]));
-        out[i].ip = t->rule_ip[i];
-        out[i].depth = t->rule_depth[i];
-        out[i].next_hop = t->rule_nh[i];
+        if (!t->rule_depth[i]) continue;
+        memset(&out[k], 0, sizeof(out[k]));
+        out[k].ip = t->rule_ip[i];
+        out[k].depth = t->rule_depth[i];
+        out[k].next_hop = t->rule_nh[i];
+        k++;
     }
-    return (int)t->n_rules;
+    return (int)k;
 }

@@ -175,6 +175,40 @@ int  cop_lpm_export_rules(const cop_lpm_table *t, cop_prefix *out, uint32_t cap)
  * miss. Setup/diagnostic use; the data path runs on the GPU. */
 int  cop_lpm_lookup_rules(const cop_lpm_table *t, const uint32_t *ips, uint32_t n, int32_t *rule_id);
 
+/* Live tables: every table, built or created empty, can be changed one rule
+ * at a time (rte_lpm_add / rte_lpm_delete / rte_lpm_delete_all /
+ * rte_lpm_is_rule_present). After each successful
+ * call the lookups, the exports above and the report equal those of a table
+ * built from the rules now held; the work is proportional to the changed
+ * prefix's subtree. A table is not thread-safe: one writer at a time, and
+ * no reader during a write.
+ *   cop_lpm_create    an empty table; cfg NULL = 1024 rules / 24 groups.
+ *   cop_lpm_add       cop_lpm_build's acceptance rules for one rule: -EINVAL
+ *                     (depth outside 1..32), -ENOSPC (max_rules held, or a
+ *                     depth > 24 rule in a /24 without a tbl8 group when all
+ *                     number_tbl8s are in use), 0 (added, or the next hop of
+ *                     a held (prefix, depth) overwritten).
+ *   cop_lpm_delete    -EINVAL for a bad depth and for a rule that is not
+ *                     held (DPDK's value, not -ENOENT); else the rule leaves
+ *                     and its addresses fall back to the longest remaining
+ *                     covering rule or to a miss. A /24's tbl8 group is in
+ *                     use while the /24 holds a rule deeper than 24; deleting
+ *                     the last one releases it (tbl8_recycle_check).
+ *   cop_lpm_is_rule_present  1 (and *next_hop, if not NULL), 0, or -EINVAL.
+ * A failed call leaves the table unchanged. Rule ids: a delete frees its id
+ * and moves no other; a new rule takes the lowest free id, so a table never
+ * deleted from keeps first-acceptance order. cop_lpm_export_rules skips
+ * freed ids; cop_lpm_export_rules_ids also returns each rule's id (out / ids
+ * NULL: the count; -ENOSPC if more than cap). cop_lpm_generation counts the
+ * successful mutations since the table was made. */
+int  cop_lpm_create(const cop_lpm_config *cfg, cop_lpm_table **out);
+int  cop_lpm_add(cop_lpm_table *t, uint32_t ip, uint8_t depth, uint32_t next_hop);
+int  cop_lpm_delete(cop_lpm_table *t, uint32_t ip, uint8_t depth);
+int  cop_lpm_delete_all(cop_lpm_table *t);
+int  cop_lpm_is_rule_present(const cop_lpm_table *t, uint32_t ip, uint8_t depth, uint32_t *next_hop);
+uint64_t cop_lpm_generation(const cop_lpm_table *t);
+int  cop_lpm_export_rules_ids(const cop_lpm_table *t, cop_prefix *out, uint32_t *ids, uint32_t cap);
+
 /* ------------------------------------------------------------------------ */
 /* Rule files (rules.json format, firewall.c:57-105,276-323)                */
 /* ------------------------------------------------------------------------ */
@@ -247,6 +281,13 @@ typedef struct cop_ctx cop_ctx;
  * Cache reads per lookup instead of one random 64 MiB probe. Results, rule
  * ids and per-rule counters are identical. */
 #define COP_CFG_FW_BKT          0x200u
+/* Live tables: the stage tables of this context accept cop_update_* patches
+ * (below). Their DIR-24-8 images keep the tbl8 groups in the plain form
+ * ($COP_TBL8=packed is ignored) with spare groups and a free list owned by
+ * the context, per-rule counters are sized to the table's max_rules, and the
+ * LDS interval buffers hold any table of up to 8192 intervals. Lookups and
+ * results are the same as without the flag. */
+#define COP_CFG_LIVE_TABLES     0x400u
 #define COP_MAX_DEMUX_PORTS     8
 
 typedef struct cop_config {
@@ -280,6 +321,65 @@ int  cop_set_routing_table(cop_ctx *ctx, const uint16_t *rt /* 65536 */);
  * firewall table with cfg (NULL = reference 1024/24, stop at first error). */
 int  cop_load_fw_rules_file(cop_ctx *ctx, const char *path, const cop_lpm_config *cfg,
                             cop_lpm_report *report);
+
+/* Rule updates without a rebuild. After cop_lpm_add / cop_lpm_delete on the
+ * table that cop_set_fw_table / cop_set_route_lpm uploaded to a
+ * COP_CFG_LIVE_TABLES context, cop_update_* brings the stage's device images
+ * to the table's current generation: only the entries of the changed
+ * prefixes' address ranges are written, by one patch kernel, from fill
+ * records that go through pinned staging; a table of at most 8192 intervals
+ * also gets its LDS interval image (about 70 KiB) copied afresh, and a table
+ * that crosses that size changes form. With COP_CFG_RULE_COUNTERS the counter
+ * word of every rule id freed since the last applied generation is zeroed in
+ * the same order. The table object must stay alive between the calls (it is
+ * recognised by identity) and is not changed by them.
+ *
+ * Ordering, one-shot launches (cop_submit, cop_submit_ring, the host paths):
+ * the call is asynchronous and stream-ordered across all lanes. Batches
+ * submitted before the call see the old rule set in every packet, batches
+ * submitted after it returns see the new one, in whichever lanes they run;
+ * no cop_sync is needed, and the call neither synchronises the device nor
+ * frees device memory. The device never holds a half-applied update: the
+ * patch waits for every lane's last launch, and every lane's next launch
+ * waits for the patch.
+ *
+ * Ordering, while a poll-mode kernel serves the context: the kernel is
+ * paused (it finishes every batch below its gates and leaves), the patch
+ * runs on the free GPU, the kernel's table parameters are refreshed and it
+ * is relaunched. Every batch is served wholly by one generation: batches
+ * waited for before the call used the old table, batches posted after it
+ * returns use the new one. -EBUSY, with the device tables untouched, when
+ * the update would change the kernel's launch geometry (the stage's table
+ * form, or the LDS bytes of its interval image), when it needs the
+ * whole-table upload below, or when it is a firewall update on a
+ * COP_CFG_RULE_COUNTERS context.
+ *
+ * Whole-table upload instead (rep->full = 1; synchronous, as cop_set_*): the
+ * context is not COP_CFG_LIVE_TABLES; the stage holds another table or none;
+ * the table's change journal (65536 mutations) no longer reaches back to the
+ * generation the context holds; the image has run out of spare tbl8 groups;
+ * or the stage's form is the trie or a bucketed one (COP_CFG_LPM_TRIE,
+ * COP_CFG_LPM_BKT for the route stage, COP_CFG_FW_BKT for the firewall).
+ *
+ * Returns 0 or -errno (-EINVAL, -EBUSY, -ENOMEM, -EIO; after -EIO the next
+ * update uploads the whole table). rep may be NULL. */
+typedef struct cop_update_report {
+    uint32_t full;          /* 1: fell back to a whole-table upload */
+    uint32_t n_changes;     /* journal entries applied */
+    uint32_t n_records;     /* patch records sent */
+    uint32_t tbl24_entries; /* tbl24 entries written by the patch kernel */
+    uint32_t tbl8_entries;  /* tbl8 entries written */
+    uint32_t groups_taken, groups_released;
+    uint64_t h2d_bytes;     /* bytes copied host to device for this update */
+} cop_update_report;
+
+int  cop_update_fw_table(cop_ctx *ctx, const cop_lpm_table *t, cop_update_report *rep);
+int  cop_update_route_lpm(cop_ctx *ctx, const cop_lpm_table *t, cop_update_report *rep);
+/* rules.json edited on disk: change t (the table the firewall stage holds)
+ * until it holds what cop_lpm_build would accept from the file under t's own
+ * limits (rules that left are deleted first, then new rules are added and
+ * changed actions overwritten), then cop_update_fw_table. */
+int  cop_update_fw_rules_file(cop_ctx *ctx, cop_lpm_table *t, const char *path, cop_update_report *rep);
 
 /* Packed header records: a batch (or ring) with stride == COP_HDR16_STRIDE
  * and no offsets holds, instead of frames, one 16-byte record per packet:
