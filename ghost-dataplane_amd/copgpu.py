@@ -70,6 +70,22 @@ class UpdateReport(Structure):
         return {k: int(getattr(self, k)) for k, _ in self._fields_}
 
 
+class AuditReport(Structure):
+    """cop_audit_report (cop_lookup_audit)."""
+    _fields_ = [("n_probes", c_uint64), ("n_mismatch", c_uint64), ("generation_table", c_uint64),
+                ("generation_device", c_uint64), ("stale", c_uint32), ("form", c_uint32),
+                ("first_ip", c_uint32), ("first_device", c_uint32), ("first_host", c_uint32),
+                ("n_bad", c_uint32)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k, _ in self._fields_}
+
+
+# bulk lookups (cop_lookup_bulk): the output word and the two image forms
+LOOKUP_HIT, LOOKUP_DROP = 0x01000000, 0x04000000
+LOOKUP_NH, LOOKUP_RULE = 0, 1
+LOOKUP_STAGE_WORDS = 1 << 20   # cop_internal.h: addresses per staging chunk of lookup_bulk_host / lookup_audit
+
 PATCH_REC_DT = np.dtype([("table", "<u4"), ("first", "<u4"), ("count", "<u4"), ("entry", "<u4")])
 
 
@@ -135,6 +151,10 @@ SIGNATURES = {
     "cop_update_fw_table": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
     "cop_update_route_lpm": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
     "cop_update_fw_rules_file": (c_int, [c_void_p, c_void_p, c_char_p, POINTER(UpdateReport)]),
+    "cop_lpm_lookup_words": (c_int, [c_void_p, c_int, c_void_p, c_uint32, c_void_p]),
+    "cop_lookup_bulk": (c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]),
+    "cop_lookup_bulk_host": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
+    "cop_lookup_audit": (c_int, [c_void_p, c_uint32, c_void_p, POINTER(AuditReport), c_void_p, c_uint32]),
     "cop_rules_load_json": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
     "cop_rules_free": (None, [c_void_p]),
     "cop_rules_write_json": (c_int, [c_char_p, c_void_p, c_uint32]),
@@ -480,6 +500,27 @@ class LpmTable:
         _check(lib().cop_lpm_lookup_rules(self.handle, _ptr(ips), len(ips), _ptr(out)))
         return out
 
+    def lookup_words(self, ips: np.ndarray, form: int = LOOKUP_NH) -> np.ndarray:
+        """cop_lpm_lookup_words: per address the exact word cop_lookup_bulk
+        returns (LOOKUP_NH: next hop | LOOKUP_HIT; LOOKUP_RULE: rule id |
+        LOOKUP_HIT | LOOKUP_DROP; 0 on a miss), from the host table as it is now."""
+        ips = np.ascontiguousarray(ips, dtype=np.uint32)
+        out = np.zeros(len(ips), dtype=np.uint32)
+        _check(lib().cop_lpm_lookup_words(self.handle, form, _ptr(ips), len(ips), _ptr(out)), what="cop_lpm_lookup_words")
+        return out
+
+    def audit_probes(self, form: int = LOOKUP_NH) -> np.ndarray:
+        """cop_lookup_audit's probe set for this table (cop_internal.h; tests)."""
+        f = lib().cop_lpm_audit_probes
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_int, POINTER(c_void_p), POINTER(c_uint32)]
+        p, n = c_void_p(), c_uint32(0)
+        _check(f(self.handle, form, byref(p), byref(n)), what="cop_lpm_audit_probes")
+        try:
+            return np.frombuffer(bytes((ctypes.c_uint8 * (n.value * 4)).from_address(p.value)), dtype=np.uint32).copy()
+        finally:
+            ctypes.CDLL(None).free(p)
+
     def intervals(self):
         m = _check(lib().cop_lpm_export_intervals(self.handle, None, None, 1 << 31))
         s = np.zeros(m, dtype=np.uint32)
@@ -719,6 +760,40 @@ class Context:
         f.restype = c_int
         f.argtypes = [c_void_p]
         return self.ROUTE_FORMS[_check(f(self.handle), self, "route_form")]
+
+    def lookup_form(self, stage: int) -> str:
+        """The table form lookup_bulk uses for a stage now (ROUTE_FORMS names;
+        "dir-packed": DIR-24-8 with packed tbl8 groups)."""
+        f = lib().cop_debug_lookup_form
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_uint32]
+        v = _check(f(self.handle, stage), self, "lookup_form")
+        return self.ROUTE_FORMS[v & 0xF] + ("-packed" if v & 0x10 else "")
+
+    def lookup_bulk(self, stage: int, ips_buf, n: int, out_buf):
+        """cop_lookup_bulk: n addresses at ips_buf (DeviceBuffer or device
+        address) through the stage's table into out_buf (may be ips_buf).
+        Asynchronous: the words are valid after sync()."""
+        def addr(x):
+            return x.addr if isinstance(x, DeviceBuffer) else int(x)
+        _check(lib().cop_lookup_bulk(self.handle, stage, c_void_p(addr(ips_buf)), n, c_void_p(addr(out_buf))), self,
+               "lookup_bulk")
+
+    def lookup_bulk_host(self, stage: int, ips: np.ndarray) -> np.ndarray:
+        """cop_lookup_bulk_host: host addresses in, their words out (synchronous)."""
+        ips = np.ascontiguousarray(ips, dtype=np.uint32)
+        out = np.zeros(len(ips), dtype=np.uint32)
+        _check(lib().cop_lookup_bulk_host(self.handle, stage, _ptr(ips), len(ips), _ptr(out)), self, "lookup_bulk_host")
+        return out
+
+    def lookup_audit(self, stage: int, table: LpmTable, bad_cap: int = 0):
+        """cop_lookup_audit: (report dict, mismatching addresses (at most
+        bad_cap, ascending)) of the stage's device image against `table`."""
+        rep = AuditReport()
+        bad = np.zeros(max(bad_cap, 1), dtype=np.uint32)
+        _check(lib().cop_lookup_audit(self.handle, stage, table.handle, byref(rep), _ptr(bad) if bad_cap else None,
+                                      bad_cap), self, "lookup_audit")
+        return rep.as_dict(), bad[: rep.n_bad]
 
     def set_routing_table(self, rt: np.ndarray):
         rt = np.ascontiguousarray(rt, dtype=np.uint16)

@@ -191,6 +191,22 @@ int cop_debug_patch(cop_ctx *c, void *tbl24_dptr, uint32_t cap24, void *tbl8_dpt
 /* tests: the route stage's table form a launch would use (COPK_TBL_*: 1 LDS
  * intervals, 2 DIR-24-8, 3 trie, 4 bucketed) */
 int cop_debug_route_form(cop_ctx *c);
+/* tests: the form cop_lookup_bulk uses for a stage (COP_STAGE_FW or
+ * COP_STAGE_LPM) now; the same COPK_TBL_* values, plus 0x10 when it is
+ * DIR-24-8 with packed tbl8 groups. -EINVAL, -ENOENT. */
+int cop_debug_lookup_form(cop_ctx *c, uint32_t stage);
+
+/* ---- bulk lookups (lpm_lookup.c) ---------------------------------------- */
+/* What a lookup word keeps of a device entry whose hit bit is set: an NH
+ * entry carries the depth in bits 26..31, a tbl8 entry valid_group in bit 25 */
+#define COP_LOOKUP_NH_MASK   0x01FFFFFFu
+#define COP_LOOKUP_RULE_MASK 0x05FFFFFFu
+/* words per staging slot of cop_lookup_bulk_host / cop_lookup_audit (4 MiB) */
+#define COP_LOOKUP_STAGE_WORDS (1u << 20)
+/* cop_lookup_audit's probe set: for every start s of the form's intervals, s
+ * and s - 1 (s > 0), plus 0xFFFFFFFF; ascending, no repeats, at most 2m + 1
+ * (malloc-ed). 0, -EINVAL, -ENOMEM. */
+int cop_lpm_audit_probes(const cop_lpm_table *t, int form, uint32_t **ips, uint32_t *n);
 
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,

@@ -220,9 +220,31 @@ struct CopKPmd {
 #define COPK_PMD_ABORT 3u     /* not every worker became resident, or a look-back timed out */
 #define COPK_PMD_PAUSED 4u    /* the host asked it to make room for other kernels; relaunched after */
 
+// cop_lpm_lookup (cop_lookup.hip): one stage's table over a stream of
+// addresses. The table fields are CopKParams' for that stage, in the one
+// form the launch names (COPK_TBL_IVT / DIR / TRIE / BKT).
+#define COPK_LOOKUP_HIT 0x01000000u
+struct CopKLookup {
+    const uint32_t *ips;      // n addresses, host byte order (4-byte aligned; may equal out)
+    uint32_t *out;            // n words: entry & mask on a hit, else 0
+    uint32_t n;
+    uint32_t ntiles;          // set by the launcher
+    uint32_t mask;            // 0x01FFFFFF (next-hop image) or 0x05FFFFFF (rule-id image)
+    uint32_t probe_nt;        // tbl24 probes as non-temporal loads ($COP_PROBE_NT)
+    uint32_t m, ib, lv, iw;   // LDS interval image (ib: also the bucketed form's index bits)
+    const uint32_t *starts, *vals;
+    const uint32_t *tbl24, *tbl8;
+    uint32_t tbl8_packed;
+    const uint32_t *tl0, *tnodes, *tleaves;
+    const uint32_t *bidx, *bpairs;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// form: COPK_TBL_*; the grid is min(tiles, ncu x resident workgroups per CU,
+// grid_cap if non-zero)
+hipError_t copk_lookup_launch(const CopKLookup *p, int form, uint32_t ncu, uint32_t grid_cap, hipStream_t stream);
 hipError_t copk_pmd_launch(const CopKPmd *p, int fw_mode, int lpm_mode, int layout, int ppt, int ext,
                            uint32_t lds_bytes, hipStream_t stream);
 // resident workgroups per CU of that kernel at lds_bytes (the occupancy API)

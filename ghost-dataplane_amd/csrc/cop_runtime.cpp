@@ -69,6 +69,17 @@ struct DevLpm {
     cop_live_img *img = nullptr;
     uint64_t tab_uid = 0;
     uint32_t grp_cap = 0;
+    bool has_table = false;         // a cop_set_* / cop_update_* table (not the empty image of cop_create)
+};
+
+// cop_lookup_bulk_host / cop_lookup_audit: pinned staging, two slots used in
+// turn (addresses up, words back through the same buffers; the kernel works
+// in place on the device side)
+struct LookupStage {
+    uint32_t *h = nullptr, *d = nullptr;
+    hipEvent_t done = nullptr;
+    uint32_t n = 0;        // words in flight (0: free)
+    uint64_t first = 0;    // their position in the caller's arrays
 };
 
 // cop_update_*: pinned staging for patch records and for the LDS interval
@@ -285,6 +296,7 @@ struct cop_ctx {
     bool probe_nt = false;     // tbl24 probes as non-temporal loads ($COP_PROBE_NT=1, experiment)
     uint32_t bkt_xbits = COP_BKT_XBITS;   // bucketed route form: 2^x buckets per interval ($COP_BKT_XBITS)
     uint32_t dbg = 0;          // $COP_DBG: timing-only kernel ablations
+    uint32_t lookup_grid = 0;  // $COP_LOOKUP_GRID: cap on the bulk-lookup kernel's workgroups (0: none; tests)
     uint32_t lds_pad = 0;      // $COP_LDS_PAD: extra LDS bytes per workgroup (occupancy experiments)
     unsigned long long *stamps = nullptr;   // dbg bit 8: per-workgroup phase stamps
     uint32_t inject_submit = 0, inject_wait = 0;   // cop_debug_inject: failures to fake (tests)
@@ -355,6 +367,7 @@ struct cop_ctx {
     int live_next = 0;
     hipEvent_t live_lane_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t live_done = nullptr;
+    LookupStage lookup_stage[2];        // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -521,6 +534,11 @@ void cop_destroy(cop_ctx *c)
     }
     for (auto &e : c->live_lane_ev)
         if (e) (void)hipEventDestroy(e);
+    for (auto &S : c->lookup_stage) {
+        if (S.h) (void)hipHostFree(S.h);
+        if (S.d) (void)hipFree(S.d);
+        if (S.done) (void)hipEventDestroy(S.done);
+    }
     if (c->live_done) (void)hipEventDestroy(c->live_done);
     delete c->gather;
     delete c;
@@ -640,6 +658,7 @@ int cop_create(const cop_config *cfg_in, cop_ctx **out)
         c->ppt_override = (v == 1 || v == 4 || v == 8) ? v : 0;
     }
     if (const char *e = getenv("COP_DBG")) c->dbg = (uint32_t)strtoul(e, nullptr, 0);
+    if (const char *e = getenv("COP_LOOKUP_GRID")) c->lookup_grid = (uint32_t)strtoul(e, nullptr, 0);
     if (const char *e = getenv("COP_LDS_PAD")) c->lds_pad = (uint32_t)strtoul(e, nullptr, 0) & ~15u;
     if (const char *e = getenv("COP_ZC_MAX")) c->zc_max = (uint32_t)strtoul(e, nullptr, 0);
     if (const char *e = getenv("COP_STREAM_ZC")) c->stream_zc = std::min(2, std::max(0, atoi(e)));
@@ -929,6 +948,7 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
         t.grp_cap = grp_cap;
     }
     t.loaded = true;
+    t.has_table = true;
     HIPCHK(c, hipDeviceSynchronize());   // the copies have landed before any lane reads them
     return 0;
 }
@@ -3311,6 +3331,202 @@ int cop_update_fw_rules_file(cop_ctx *c, cop_lpm_table *t, const char *path, cop
     cop_lpm_free(want);
     if (rc) return set_err(c, rc, "rules file %s: table change failed: %d", path, rc);
     return cop_update_fw_table(c, t, rep);
+}
+
+// ---- bulk lookups (cop_lookup.hip) -----------------------------------------
+// cop_lookup_bulk runs one stage's table over a stream of addresses, in the
+// form a pipeline launch would use for that stage alone (pick_mode). It is a
+// launch on a lane like any other, so cop_update_* orders it for free: the
+// patch waits for every lane's last launch, every lane's next launch waits
+// for the patch, and the table fields below are read at the call, as
+// fill_launch reads them.
+
+static int lookup_stage_of(cop_ctx *c, uint32_t stage, DevLpm **t_out, int *form_out, uint32_t *mask_out)
+{
+    if (stage != COP_STAGE_FW && stage != COP_STAGE_LPM)
+        return set_err(c, -EINVAL, "lookup: stage 0x%x is not exactly COP_STAGE_FW or COP_STAGE_LPM", stage);
+    const bool is_fw = stage == COP_STAGE_FW;
+    DevLpm &t = is_fw ? c->fw : c->lpm;
+    if (!t.has_table)
+        return set_err(c, -ENOENT, "lookup: the %s stage holds no table (cop_set_%s first)", is_fw ? "firewall" : "route",
+                       is_fw ? "fw_table" : "route_lpm");
+    *t_out = &t;
+    *form_out = pick_mode(c, t, true, (c->cfg.flags & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24)) != 0);
+    *mask_out = is_fw ? COP_LOOKUP_RULE_MASK : COP_LOOKUP_NH_MASK;
+    return 0;
+}
+
+int cop_debug_lookup_form(cop_ctx *c, uint32_t stage)
+{
+    if (!c) return -EINVAL;
+    DevLpm *t = nullptr;
+    int form = 0;
+    uint32_t mask = 0;
+    if (int rc = lookup_stage_of(c, stage, &t, &form, &mask)) return rc;
+    return form | ((form == COPK_TBL_DIR && t->tbl8_packed) ? 0x10 : 0);
+}
+
+static int lookup_launch(cop_ctx *c, hipStream_t s, const DevLpm &t, int form, uint32_t mask, const uint32_t *ips,
+                         uint32_t n, uint32_t *out)
+{
+    CopKLookup p;
+    memset(&p, 0, sizeof(p));
+    p.ips = ips;
+    p.out = out;
+    p.n = n;
+    p.mask = mask;
+    p.probe_nt = c->probe_nt ? 1u : 0u;
+    p.m = form == COPK_TBL_IVT ? t.m : 0;
+    p.ib = t.ib;
+    p.lv = t.lv;
+    p.iw = form == COPK_TBL_IVT ? t.iw : 0;
+    p.starts = t.starts;
+    p.vals = t.vals;
+    p.tbl24 = t.tbl24;
+    p.tbl8 = t.tbl8;
+    p.tbl8_packed = t.tbl8_packed ? 1u : 0u;
+    p.tl0 = t.tl0;
+    p.tnodes = t.tnodes;
+    p.tleaves = t.tleaves;
+    p.bidx = t.bidx;
+    p.bpairs = t.bpairs;
+    const hipError_t e = copk_lookup_launch(&p, form, (uint32_t)c->ncu, c->lookup_grid, s);
+    if (e != hipSuccess) return set_err(c, -EIO, "lookup launch: %s", hipGetErrorString(e));
+    return 0;
+}
+
+int cop_lookup_bulk(cop_ctx *c, uint32_t stage, const uint32_t *ips, uint32_t n, uint32_t *out)
+{
+    if (!c) return -EINVAL;
+    DevLpm *t = nullptr;
+    int form = 0;
+    uint32_t mask = 0;
+    if (int rc = lookup_stage_of(c, stage, &t, &form, &mask)) return rc;
+    if (n == 0) return 0;
+    if (!ips || !out) return set_err(c, -EINVAL, "lookup: null pointer");
+    const uintptr_t a = (uintptr_t)ips, b = (uintptr_t)out;
+    if ((a | b) & 3u) return set_err(c, -EINVAL, "lookup: ips and out must be 4-byte aligned");
+    const uint64_t bytes = (uint64_t)n * 4;
+    if (a != b && a < b + bytes && b < a + bytes)
+        return set_err(c, -EINVAL, "lookup: ips and out overlap (only out == ips is allowed)");
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->pmd) {
+        // another kernel is not guaranteed a place beside the poll-mode
+        // kernel: pause it, look up on the free GPU, relaunch it
+        if (int rc = pmd_pause(c)) return rc;
+        int rc = lookup_launch(c, c->stream, *t, form, mask, ips, n, out);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "lookup sync");
+        const int rrc = pmd_resume(c);
+        return rc ? rc : rrc;
+    }
+    Lane &L = c->lane[c->next_lane];
+    c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    return lookup_launch(c, L.s, *t, form, mask, ips, n, out);
+}
+
+// Host arrays through the two staging slots: chunk k goes up, is looked up in
+// place and comes back on lane k % n_lanes while the host copies chunk k - 1
+// out and chunk k + 1 in. Synchronous. With a poll-mode kernel: paused for
+// the whole call, everything on lane 0.
+static int lookup_host_run(cop_ctx *c, DevLpm &t, int form, uint32_t mask, const uint32_t *ips, uint64_t n,
+                           uint32_t *out)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    for (auto &S : c->lookup_stage) {
+        if (!S.h) HIPCHK(c, hipHostMalloc(&S.h, (size_t)COP_LOOKUP_STAGE_WORDS * 4, hipHostMallocDefault));
+        if (!S.d) HIPCHK(c, hipMalloc(&S.d, (size_t)COP_LOOKUP_STAGE_WORDS * 4));
+        if (!S.done) HIPCHK(c, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
+    }
+    if (int rc = pmd_pause(c)) return rc;
+    int rc = 0;
+    auto drain = [&](LookupStage &S) {
+        if (!S.n) return;
+        if (hipEventSynchronize(S.done) != hipSuccess) {
+            if (!rc) rc = set_err(c, -EIO, "lookup staging: wait failed");
+        } else if (!rc) {
+            memcpy(out + S.first, S.h, (size_t)S.n * 4);
+        }
+        S.n = 0;
+    };
+    uint64_t done = 0;
+    for (uint32_t k = 0; done < n && !rc; k++) {
+        LookupStage &S = c->lookup_stage[k & 1u];
+        drain(S);
+        if (rc) break;
+        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - done, COP_LOOKUP_STAGE_WORDS);
+        memcpy(S.h, ips + done, (size_t)cnt * 4);
+        hipStream_t s = c->pmd ? c->stream : c->lane[k % (uint32_t)c->n_lanes].s;
+        hipError_t e = hipMemcpyAsync(S.d, S.h, (size_t)cnt * 4, hipMemcpyHostToDevice, s);
+        if (e == hipSuccess) {
+            rc = lookup_launch(c, s, t, form, mask, S.d, cnt, S.d);
+            if (!rc) e = hipMemcpyAsync(S.h, S.d, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+        }
+        // (the event is recorded whatever was enqueued, so the slot can be waited for)
+        const hipError_t e2 = hipEventRecord(S.done, s);
+        if ((e != hipSuccess || e2 != hipSuccess) && !rc)
+            rc = set_err(c, -EIO, "lookup staging: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+        S.first = done;
+        S.n = e2 == hipSuccess ? cnt : 0;
+        done += cnt;
+    }
+    // the older slot first (its words sit earlier in out; order is irrelevant to correctness)
+    for (auto &S : c->lookup_stage) drain(S);
+    const int rrc = pmd_resume(c);
+    return rc ? rc : rrc;
+}
+
+int cop_lookup_bulk_host(cop_ctx *c, uint32_t stage, const uint32_t *ips, uint64_t n, uint32_t *out)
+{
+    if (!c) return -EINVAL;
+    DevLpm *t = nullptr;
+    int form = 0;
+    uint32_t mask = 0;
+    if (int rc = lookup_stage_of(c, stage, &t, &form, &mask)) return rc;
+    if (n == 0) return 0;
+    if (!ips || !out) return set_err(c, -EINVAL, "lookup: null pointer");
+    if (((uintptr_t)ips | (uintptr_t)out) & 3u) return set_err(c, -EINVAL, "lookup: ips and out must be 4-byte aligned");
+    return lookup_host_run(c, *t, form, mask, ips, n, out);
+}
+
+int cop_lookup_audit(cop_ctx *c, uint32_t stage, const cop_lpm_table *tab, cop_audit_report *rep, uint32_t *bad_ips,
+                     uint32_t bad_cap)
+{
+    if (!c || !tab || !rep) return -EINVAL;
+    memset(rep, 0, sizeof(*rep));
+    DevLpm *t = nullptr;
+    int form = 0;
+    uint32_t mask = 0;
+    if (int rc = lookup_stage_of(c, stage, &t, &form, &mask)) return rc;
+    if (int rc = sync_lanes(c)) return rc;
+    const int tform = stage == COP_STAGE_FW ? COP_LOOKUP_RULE : COP_LOOKUP_NH;
+    rep->form = (uint32_t)form;
+    rep->generation_table = tab->generation;
+    rep->generation_device = t->img ? cop_live_img_generation(t->img) : 0;
+    rep->stale = (t->img && (t->tab_uid != tab->uid || rep->generation_device != tab->generation)) ? 1u : 0u;
+    uint32_t *ips = nullptr, n = 0;
+    int rc = cop_lpm_audit_probes(tab, tform, &ips, &n);
+    if (rc) return set_err(c, rc, "audit: probe set: %d", rc);
+    uint32_t *dev = (uint32_t *)malloc((size_t)n * 4), *host = (uint32_t *)malloc((size_t)n * 4);
+    if (!dev || !host) rc = set_err(c, -ENOMEM, "audit: out of memory");
+    if (!rc) rc = lookup_host_run(c, *t, form, mask, ips, n, dev);
+    if (!rc && (rc = cop_lpm_lookup_words(tab, tform, ips, n, host)) != 0) rc = set_err(c, rc, "audit: host words: %d", rc);
+    if (!rc) {
+        rep->n_probes = n;
+        for (uint32_t i = 0; i < n; i++) {   // the probes ascend: so do the reported addresses
+            if (dev[i] == host[i]) continue;
+            if (!rep->n_mismatch) {
+                rep->first_ip = ips[i];
+                rep->first_device = dev[i];
+                rep->first_host = host[i];
+            }
+            rep->n_mismatch++;
+            if (bad_ips && rep->n_bad < bad_cap) bad_ips[rep->n_bad++] = ips[i];
+        }
+    }
+    free(ips);
+    free(dev);
+    free(host);
+    return rc;
 }
 
 /* tests: the patch kernel alone on caller buffers (cop_internal.h) */

@@ -381,6 +381,79 @@ int  cop_update_route_lpm(cop_ctx *ctx, const cop_lpm_table *t, cop_update_repor
  * changed actions overwritten), then cop_update_fw_table. */
 int  cop_update_fw_rules_file(cop_ctx *ctx, cop_lpm_table *t, const char *path, cop_update_report *rep);
 
+/* ------------------------------------------------------------------------ */
+/* Bulk lookups (rte_lpm_lookup_bulk on the device) and table audit         */
+/* ------------------------------------------------------------------------ */
+
+/* An array of IPv4 addresses (host byte order) in, one word per address out,
+ * straight from a stage's device table: no frames, no pipeline, no counters.
+ * The word is the same from every device form of the table and from the host
+ * reference cop_lpm_lookup_words:
+ *   route stage / COP_LOOKUP_NH     hit:  next_hop | COP_LOOKUP_HIT
+ *   firewall stage / COP_LOOKUP_RULE hit: rule_id | COP_LOOKUP_HIT
+ *                                         | (action != 0 ? COP_LOOKUP_DROP : 0)
+ *   miss: exactly 0. Every other bit is zero.
+ * rule_id is the id of cop_lpm_export_rules_ids (the per-rule counter index).
+ * Relation to DPDK: out[i] & 0x00FFFFFF and the COP_LOOKUP_HIT flag
+ * (RTE_LPM_LOOKUP_SUCCESS) are what rte_lpm_lookup_bulk gives for a table
+ * holding the same rules; DPDK's depth and valid_group bits are not
+ * reproduced. */
+#define COP_LOOKUP_HIT  0x01000000u   /* == RTE_LPM_LOOKUP_SUCCESS */
+#define COP_LOOKUP_DROP 0x04000000u   /* firewall form: the matching rule's action is non-zero */
+#define COP_LOOKUP_NH   0             /* form of the route stage's image */
+#define COP_LOOKUP_RULE 1             /* form of the firewall stage's image */
+
+/* Host reference: the exact word the device returns, from the host table as
+ * it is now (after any cop_lpm_add / cop_lpm_delete). 0, -EINVAL (NULL, or a
+ * form other than the two above), -ENOMEM. */
+int  cop_lpm_lookup_words(const cop_lpm_table *t, int form, const uint32_t *ips, uint32_t n, uint32_t *out);
+
+/* Device lookup. stage is exactly COP_STAGE_FW or COP_STAGE_LPM (else
+ * -EINVAL); the stage need not be in cfg.stages but must hold a table
+ * (-ENOENT). ips / out are device pointers (or mapped host memory), 4-byte
+ * aligned (-EINVAL); when both are 16-byte aligned the kernel moves 16 bytes
+ * per lane. out == ips (in place) is allowed, any other overlap is -EINVAL.
+ * n == 0 returns 0 and launches nothing.
+ *
+ * The table form is the one a pipeline launch would use for that stage alone
+ * (the LDS interval image, else trie / bucketed when built, else DIR-24-8
+ * with plain or packed tbl8 groups), following the context's flags.
+ *
+ * Ordering: asynchronous, queued on the context's next launch lane
+ * (round-robin, as cop_submit); outputs are valid after cop_sync. It is
+ * ordered with cop_update_* like any launch: a lookup queued before
+ * cop_update_* is called reads the old image for every address, one queued
+ * after it returns reads the new one; no cop_sync is needed in between. No
+ * counter is touched (cop_counters, port stats, per-rule hits).
+ *
+ * While a poll-mode kernel serves the context the call is synchronous: the
+ * kernel is paused, the lookup runs on the free GPU, the kernel is
+ * relaunched (as cop_counters_snapshot does); the outputs are valid on
+ * return. */
+int  cop_lookup_bulk(cop_ctx *ctx, uint32_t stage, const uint32_t *ips, uint32_t n, uint32_t *out);
+/* The same over host arrays of any length: pinned staging in chunks, two
+ * slots in turn; synchronous. out == ips is allowed. */
+int  cop_lookup_bulk_host(cop_ctx *ctx, uint32_t stage, const uint32_t *ips, uint64_t n, uint32_t *out);
+
+/* Does the stage's device image answer as host table t does, right now?
+ * Probes: for every start s of t's intervals in the stage's form, s and
+ * s - 1 (s > 0), plus 0xFFFFFFFF (at most 2m + 1 addresses: every interval
+ * is probed at both ends). They go through cop_lookup_bulk_host's staging
+ * and are compared with cop_lpm_lookup_words. Synchronous; waits for the
+ * context's queued work first. Returns 0 with the report filled (a mismatch
+ * is a finding, not an error) or cop_lookup_bulk's errors. Up to bad_cap
+ * mismatching addresses, ascending, are written to bad_ips (may be NULL). */
+typedef struct cop_audit_report {
+    uint64_t n_probes, n_mismatch;
+    uint64_t generation_table, generation_device; /* device: 0 when the stage is not live */
+    uint32_t stale;          /* live stage holds another generation (or another table) than t */
+    uint32_t form;           /* device form the lookups ran in (0 off,1 LDS,2 DIR-24-8,3 trie,4 bucketed) */
+    uint32_t first_ip, first_device, first_host; /* first mismatch, if any */
+    uint32_t n_bad;          /* entries written to bad_ips */
+} cop_audit_report;
+int  cop_lookup_audit(cop_ctx *ctx, uint32_t stage, const cop_lpm_table *t, cop_audit_report *rep,
+                      uint32_t *bad_ips, uint32_t bad_cap);
+
 /* Packed header records: a batch (or ring) with stride == COP_HDR16_STRIDE
  * and no offsets holds, instead of frames, one 16-byte record per packet:
  * frame bytes 12..15 (EtherType, version/IHL, TOS) followed by bytes 24..35
