@@ -151,6 +151,8 @@ SIGNATURES = {
     "cop_update_fw_table": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
     "cop_update_route_lpm": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
     "cop_update_fw_rules_file": (c_int, [c_void_p, c_void_p, c_char_p, POINTER(UpdateReport)]),
+    "cop_replace_fw_table": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
+    "cop_replace_route_lpm": (c_int, [c_void_p, c_void_p, POINTER(UpdateReport)]),
     "cop_lpm_lookup_words": (c_int, [c_void_p, c_int, c_void_p, c_uint32, c_void_p]),
     "cop_lookup_bulk": (c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]),
     "cop_lookup_bulk_host": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
@@ -638,6 +640,44 @@ def patch_apply_host(tbl24: np.ndarray, tbl8: np.ndarray, recs: np.ndarray):
     _check(f(_ptr(tbl24), len(tbl24), _ptr(tbl8), len(tbl8), _ptr(recs), len(recs)), what="cop_patch_apply_host")
 
 
+PAINT_CHUNK = 4096   # cop_kernels.h COPK_PAINT_CHUNK: /24 blocks per workgroup of the paint kernel
+
+
+def paint_plan(table: LpmTable, form: int = 0):
+    """cop_lpm_paint_plan: (starts, entries, ext24) of a form (0: next hop,
+    1: rule id), the paint kernel's inputs; len(ext24) is the form's n_ext."""
+    f = lib().cop_lpm_paint_plan
+    f.restype = c_int
+    f.argtypes = [c_void_p, c_int, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32), POINTER(c_void_p),
+                  POINTER(c_uint32)]
+    ps, pe, px, niv, n_ext = c_void_p(), c_void_p(), c_void_p(), c_uint32(0), c_uint32(0)
+    _check(f(table.handle, form, byref(ps), byref(pe), byref(niv), byref(px), byref(n_ext)), what="cop_lpm_paint_plan")
+
+    def take(p, n):
+        try:
+            return np.frombuffer(bytes((ctypes.c_uint8 * (n * 4)).from_address(p.value)), dtype=np.uint32).copy()
+        finally:
+            ctypes.CDLL(None).free(p)
+    return take(ps, niv.value), take(pe, niv.value), take(px, n_ext.value)
+
+
+def paint_host(starts: np.ndarray, entries: np.ndarray, ext24: np.ndarray, cap_groups: int, fill: int = 0):
+    """cop_paint_host, the paint kernel's mirror: (tbl24, tbl8) with tbl8 of
+    cap_groups * 256 entries, both pre-filled with `fill`."""
+    starts = np.ascontiguousarray(starts, dtype=np.uint32)
+    entries = np.ascontiguousarray(entries, dtype=np.uint32)
+    ext24 = np.ascontiguousarray(ext24, dtype=np.uint32)
+    assert len(starts) == len(entries)
+    t24 = np.full(1 << 24, fill, dtype=np.uint32)
+    t8 = np.full(max(cap_groups, 1) * 256, fill, dtype=np.uint32)
+    f = lib().cop_paint_host
+    f.restype = c_int
+    f.argtypes = [c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+    _check(f(_ptr(starts), _ptr(entries), len(starts), _ptr(ext24) if len(ext24) else None, len(ext24), _ptr(t24),
+             _ptr(t8), cap_groups), what="cop_paint_host")
+    return t24, t8[: cap_groups * 256]
+
+
 ALLOC_UNCACHED, ALLOC_FINEGRAINED = 1, 2
 
 
@@ -825,6 +865,29 @@ class Context:
         rep = self._update(lib().cop_update_fw_rules_file, "update_fw_rules_file", t.handle, path.encode())
         t._refresh()
         return rep
+
+    def replace_fw_table(self, t: LpmTable) -> dict:
+        """The firewall stage takes table t, whatever it held
+        (cop_replace_fw_table): painted on the device in stream order, no
+        sync needed; returns the update report."""
+        return self._update(lib().cop_replace_fw_table, "replace_fw_table", t.handle)
+
+    def replace_route_lpm(self, t: LpmTable) -> dict:
+        return self._update(lib().cop_replace_route_lpm, "replace_route_lpm", t.handle)
+
+    def debug_paint(self, starts: np.ndarray, entries: np.ndarray, ext24: np.ndarray, tbl24: DeviceBuffer,
+                    tbl8: DeviceBuffer, cap_groups: int):
+        """The paint kernel alone on two caller buffers (tests): tbl24 of 2^24
+        entries, tbl8 of at least cap_groups * 256."""
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        entries = np.ascontiguousarray(entries, dtype=np.uint32)
+        ext24 = np.ascontiguousarray(ext24, dtype=np.uint32)
+        assert len(starts) == len(entries) and tbl24.nbytes >= 4 << 24 and tbl8.nbytes >= cap_groups * 1024
+        f = lib().cop_debug_paint
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p, c_uint32, c_void_p, c_void_p, c_uint32]
+        _check(f(self.handle, _ptr(starts), _ptr(entries), len(starts), _ptr(ext24) if len(ext24) else None, len(ext24),
+                 tbl24.ptr, tbl8.ptr, cap_groups), self, "debug_paint")
 
     def debug_patch(self, tbl24: DeviceBuffer, tbl8: DeviceBuffer, recs: np.ndarray) -> int:
         """The patch kernel alone on two caller buffers (tests); returns the

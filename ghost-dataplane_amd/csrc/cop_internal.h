@@ -188,6 +188,28 @@ int cop_patch_apply_host(uint32_t *tbl24, uint32_t cap24, uint32_t *tbl8, uint32
 int cop_debug_patch(cop_ctx *c, void *tbl24_dptr, uint32_t cap24, void *tbl8_dptr, uint32_t cap8,
                     const cop_patch_rec *recs, uint32_t n);
 
+/* ---- whole-image paint (lpm_build.c, cop_paint.hip) ----------------------- */
+/* /24 blocks one workgroup of the paint kernel owns (COPK_PAINT_CHUNK) */
+#define COP_PAINT_CHUNK 4096u
+/* What the paint kernel reads for a form's DIR-24-8 image: the unmerged
+ * (start, entry) intervals cop_lpm_form_fill_dir24 paints from, and the
+ * ascending /24 blocks that hold an interval start past their first address
+ * (the extended blocks: ext24[g] owns tbl8 group g, fill_dir24's numbering;
+ * *n_ext == cop_lpm_form_n_ext). The three arrays are malloc-ed (ext24 has at
+ * least one word). 0, -EINVAL, -ENOMEM. */
+int cop_lpm_paint_plan(const cop_lpm_table *t, int form, uint32_t **starts, uint32_t **entries, uint32_t *niv,
+                       uint32_t **ext24, uint32_t *n_ext);
+/* Host mirror of the paint kernel, chunk by chunk and with a search per entry
+ * as the kernel does it: all 2^24 tbl24 entries, tbl8 groups 0 .. n_ext - 1,
+ * zeros in groups n_ext .. cap_groups - 1. -EINVAL (and nothing written) for
+ * niv == 0, starts[0] != 0 or n_ext > cap_groups. */
+int cop_paint_host(const uint32_t *starts, const uint32_t *entries, uint32_t niv, const uint32_t *ext24,
+                   uint32_t n_ext, uint32_t *tbl24, uint32_t *tbl8, uint32_t cap_groups);
+/* tests: the paint kernel alone, on device buffers the caller allocated
+ * (16-byte aligned; tbl24: 2^24 entries, tbl8: cap_groups * 256); synchronous */
+int cop_debug_paint(cop_ctx *c, const uint32_t *starts, const uint32_t *entries, uint32_t niv, const uint32_t *ext24,
+                    uint32_t n_ext, void *tbl24_dptr, void *tbl8_dptr, uint32_t cap_groups);
+
 /* tests: the route stage's table form a launch would use (COPK_TBL_*: 1 LDS
  * intervals, 2 DIR-24-8, 3 trie, 4 bucketed) */
 int cop_debug_route_form(cop_ctx *c);

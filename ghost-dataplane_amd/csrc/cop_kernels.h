@@ -265,6 +265,16 @@ hipError_t copk_snapshot(unsigned long long *src, uint32_t n_words, unsigned lon
 #define COPK_PATCH_SPAN 1024u
 hipError_t copk_patch_launch(const void *recs, uint32_t n, uint32_t *tbl24, uint32_t cap24, uint32_t *tbl8,
                              uint32_t cap8, hipStream_t stream);
+// cop_lpm_paint (cop_paint.hip): a whole DIR-24-8 image from niv sorted
+// intervals (starts[0] == 0, entries: the device entry of each) and the
+// ascending list of the n_ext extended /24 blocks, all device memory: every
+// one of the 2^24 tbl24 entries, tbl8 groups 0 .. n_ext - 1, zeros in groups
+// n_ext .. cap_groups - 1, nothing beyond cap_groups * 256. One workgroup per
+// COPK_PAINT_CHUNK consecutive blocks, then one wave per tbl8 group. tbl24 and
+// tbl8 16-byte aligned; n_ext <= cap_groups.
+#define COPK_PAINT_CHUNK 4096u
+hipError_t copk_paint_launch(const uint32_t *starts, const uint32_t *entries, uint32_t niv, const uint32_t *ext24,
+                             uint32_t n_ext, uint32_t *tbl24, uint32_t *tbl8, uint32_t cap_groups, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

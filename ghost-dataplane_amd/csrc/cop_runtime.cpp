@@ -367,7 +367,21 @@ struct cop_ctx {
     int live_next = 0;
     hipEvent_t live_lane_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t live_done = nullptr;
-    LookupStage lookup_stage[2];        // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
+    // cop_replace_*: the paint kernel's inputs (starts | entries | ext24) go
+    // through one pinned buffer and one device buffer sized to the largest
+    // plan so far; `paint_copied` tells when the copy engine has read the
+    // pinned side. Buffers a replacement outgrew may still be read by queued
+    // work: they wait here for the next cop_set_* or cop_destroy.
+    uint32_t *paint_h = nullptr, *paint_d = nullptr;
+    size_t paint_words = 0;
+    hipEvent_t paint_copied = nullptr;
+    bool paint_used = false;
+    struct Retired {
+        void *p;
+        bool pinned;
+    };
+    std::vector<Retired> retired;
+    LookupStage lookup_stage[2];       // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -469,6 +483,16 @@ static void free_lpm(DevLpm &t)
     t = DevLpm();
 }
 
+// buffers cop_replace_* outgrew; the caller has made sure no queued work reads them
+static void free_retired(cop_ctx *c)
+{
+    for (auto &r : c->retired) {
+        if (r.pinned) (void)hipHostFree(r.p);
+        else (void)hipFree(r.p);
+    }
+    c->retired.clear();
+}
+
 static void coll_destroy(cop_ctx *c);
 
 void cop_destroy(cop_ctx *c)
@@ -540,6 +564,10 @@ void cop_destroy(cop_ctx *c)
         if (S.done) (void)hipEventDestroy(S.done);
     }
     if (c->live_done) (void)hipEventDestroy(c->live_done);
+    free_retired(c);
+    if (c->paint_h) (void)hipHostFree(c->paint_h);
+    if (c->paint_d) (void)hipFree(c->paint_d);
+    if (c->paint_copied) (void)hipEventDestroy(c->paint_copied);
     delete c->gather;
     delete c;
 }
@@ -889,6 +917,7 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
                       bool want_bkt = false)
 {
     if (int rc = sync_lanes(c)) return rc;
+    free_retired(c);   // what cop_replace_* outgrew: nothing queued reads it any more
     free_lpm(t);
     // interval form for LDS
     uint32_t *s = nullptr, *v = nullptr;
@@ -3183,6 +3212,50 @@ static int live_apply(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, int form,
     return 0;
 }
 
+// One-shot ordering of a table change on lane 0's stream: it waits for every
+// other lane's last launch ...
+static int live_order_begin(cop_ctx *c)
+{
+    hipError_t e = hipSuccess;
+    for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) {
+        e = hipEventRecord(c->live_lane_ev[l], c->lane[l].s);
+        if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->live_lane_ev[l], 0);
+    }
+    return e == hipSuccess ? 0 : set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+}
+
+// ... and every other lane's next launch waits for it
+static int live_order_end(cop_ctx *c)
+{
+    hipError_t e = hipEventRecord(c->live_done, c->stream);
+    for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) e = hipStreamWaitEvent(c->lane[l].s, c->live_done, 0);
+    return e == hipSuccess ? 0 : set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+}
+
+// the poll-mode kernel's stored launch parameters: the table fields, as fill_launch sets them
+static void pmd_refresh_tables(cop_ctx *c, cop_pmd *m)
+{
+    CopKParams &p = m->P.k;
+    p.fw_m = m->fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
+    p.fw_ib = c->fw.ib;
+    p.fw_lv = c->fw.lv;
+    p.fw_iw = m->fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
+    p.fw_starts = c->fw.starts;
+    p.fw_vals = c->fw.vals;
+    p.fw_tbl24 = c->fw.tbl24;
+    p.fw_tbl8 = c->fw.tbl8;
+    p.fw_tbl8_packed = c->fw.tbl8_packed ? 1u : 0u;
+    p.lpm_m = m->lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
+    p.lpm_ib = c->lpm.ib;
+    p.lpm_lv = c->lpm.lv;
+    p.lpm_iw = m->lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
+    p.lpm_starts = c->lpm.starts;
+    p.lpm_vals = c->lpm.vals;
+    p.lpm_tbl24 = c->lpm.tbl24;
+    p.lpm_tbl8 = c->lpm.tbl8;
+    p.lpm_tbl8_packed = c->lpm.tbl8_packed ? 1u : 0u;
+}
+
 static int live_update(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_update_report *rep_out)
 {
     if (!c || !tab) return -EINVAL;
@@ -3251,31 +3324,16 @@ static int live_update(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_upd
         if ((rc = pmd_pause(c)) == 0) {
             rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
             if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "patch sync");
-            // the stored launch parameters: the table fields, as fill_launch sets them
-            CopKParams &p = m->P.k;
-            p.fw_m = m->fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
-            p.fw_ib = c->fw.ib;
-            p.fw_lv = c->fw.lv;
-            p.fw_iw = m->fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
-            p.lpm_m = m->lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
-            p.lpm_ib = c->lpm.ib;
-            p.lpm_lv = c->lpm.lv;
-            p.lpm_iw = m->lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
+            pmd_refresh_tables(c, m);
             const int rrc = pmd_resume(c);
             if (!rc) rc = rrc;
         }
     } else if (!rc) {
-        hipError_t e = hipSuccess;
-        for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) {
-            e = hipEventRecord(c->live_lane_ev[l], c->lane[l].s);
-            if (e == hipSuccess) e = hipStreamWaitEvent(c->stream, c->live_lane_ev[l], 0);
-        }
-        if (e != hipSuccess) rc = set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+        rc = live_order_begin(c);
         if (!rc) rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
         // every lane's next launch comes after whatever part of the patch was enqueued
-        e = hipEventRecord(c->live_done, c->stream);
-        for (int l = 1; l < c->n_lanes && e == hipSuccess; l++) e = hipStreamWaitEvent(c->lane[l].s, c->live_done, 0);
-        if (e != hipSuccess && !rc) rc = set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
+        const int orc = live_order_end(c);
+        if (!rc) rc = orc;
     }
     free(chg);
     free(recs);
@@ -3298,6 +3356,241 @@ int cop_update_fw_table(cop_ctx *c, const cop_lpm_table *t, cop_update_report *r
 int cop_update_route_lpm(cop_ctx *c, const cop_lpm_table *t, cop_update_report *rep)
 {
     return live_update(c, false, t, rep);
+}
+
+// ---- whole-table replacement (cop_replace_*) --------------------------------
+// The stage takes table `tab`, whatever it held, in the order cop_update_*
+// keeps: the DIR-24-8 image is painted on the device from the table's
+// intervals (cop_paint.hip), the LDS interval image copied behind it, the
+// firewall's per-rule counter words zeroed, all on lane 0's stream between
+// the launches of every lane. Nothing is freed and nothing waits for the
+// device: a buffer the new table outgrows is replaced by a fresh allocation
+// and retired (c->retired), since launches queued earlier still read it.
+
+static_assert(COP_PAINT_CHUNK == COPK_PAINT_CHUNK, "the host mirror paints the kernel's chunks");
+
+// the tbl8 capacity (groups) of a live image of a table: upload_lpm's rule
+static uint32_t live_grp_cap(const cop_lpm_table *tab, uint32_t n_ext)
+{
+    return (uint32_t)std::max<uint64_t>(
+        std::max(n_ext, 1u), std::min<uint64_t>(2 * (uint64_t)tab->cfg.number_tbl8s, (uint64_t)n_ext + std::max(256u, n_ext / 2)));
+}
+
+// the paint kernel's inputs in one buffer: starts | entries | ext24, each
+// padded to 16 bytes
+struct PaintPlan {
+    uint32_t *starts = nullptr, *entries = nullptr, *ext24 = nullptr;
+    uint32_t niv = 0, n_ext = 0;
+    uint32_t off_e = 0, off_x = 0, words = 0;
+    ~PaintPlan()
+    {
+        free(starts);
+        free(entries);
+        free(ext24);
+    }
+};
+
+static int paint_plan(cop_ctx *c, const cop_lpm_table *tab, int form, PaintPlan &P)
+{
+    const int rc = cop_lpm_paint_plan(tab, form, &P.starts, &P.entries, &P.niv, &P.ext24, &P.n_ext);
+    if (rc) return set_err(c, rc, "paint plan: %d", rc);
+    P.off_e = (P.niv + 3u) & ~3u;
+    P.off_x = 2 * P.off_e;
+    P.words = P.off_x + std::max((P.n_ext + 3u) & ~3u, 4u);
+    return 0;
+}
+
+// room for the plan in the pinned and the device staging buffer (an outgrown
+// pair is retired), and the plan in the pinned one
+static int paint_stage(cop_ctx *c, const PaintPlan &P)
+{
+    if (!c->paint_copied) HIPCHK(c, hipEventCreateWithFlags(&c->paint_copied, hipEventDisableTiming));
+    if (c->paint_words < P.words) {
+        const size_t want = std::max<size_t>((size_t)P.words + P.words / 4, 1u << 16);
+        uint32_t *h = nullptr, *d = nullptr;
+        HIPCHK(c, hipHostMalloc(&h, want * 4, hipHostMallocDefault));
+        if (hipMalloc(&d, want * 4) != hipSuccess) {
+            (void)hipHostFree(h);   // never handed to the device
+            return set_err(c, -ENOMEM, "paint staging: %zu bytes", want * 4);
+        }
+        if (c->paint_h) c->retired.push_back({c->paint_h, true});
+        if (c->paint_d) c->retired.push_back({c->paint_d, false});
+        c->paint_h = h;
+        c->paint_d = d;
+        c->paint_words = want;
+        c->paint_used = false;
+    }
+    // the one host wait: the copy engine may still read the last plan
+    if (c->paint_used) HIPCHK(c, hipEventSynchronize(c->paint_copied));
+    memcpy(c->paint_h, P.starts, (size_t)P.niv * 4);
+    memcpy(c->paint_h + P.off_e, P.entries, (size_t)P.niv * 4);
+    if (P.n_ext) memcpy(c->paint_h + P.off_x, P.ext24, (size_t)P.n_ext * 4);
+    return 0;
+}
+
+// the staged plan up and the kernel behind it, on lane 0's stream
+static int paint_send(cop_ctx *c, const PaintPlan &P, uint32_t *tbl24, uint32_t *tbl8, uint32_t cap_groups,
+                      cop_update_report *rep)
+{
+    const size_t bytes = (size_t)(P.off_x + P.n_ext) * 4;
+    HIPCHK(c, hipMemcpyAsync(c->paint_d, c->paint_h, bytes, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->paint_copied, c->stream));
+    c->paint_used = true;
+    const hipError_t e = copk_paint_launch(c->paint_d, c->paint_d + P.off_e, P.niv, c->paint_d + P.off_x, P.n_ext, tbl24,
+                                           tbl8, cap_groups, c->stream);
+    if (e != hipSuccess) return set_err(c, -EIO, "paint launch: %s", hipGetErrorString(e));
+    rep->n_records = P.niv;
+    rep->tbl24_entries = 1u << 24;
+    rep->tbl8_entries = P.n_ext * 256u;
+    rep->groups_taken = P.n_ext;
+    rep->h2d_bytes += bytes;
+    return 0;
+}
+
+// the device side of one replacement; the caller has made the GPU free of
+// readers of this stage's images in c->stream's order
+static int replace_apply(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, int form, bool ivt_new, const PaintPlan &P,
+                         uint32_t grp_cap, cop_update_report *rep)
+{
+    if (int rc = paint_send(c, P, t.tbl24, t.tbl8, grp_cap, rep)) return rc;
+    if (ivt_new) {
+        if (int rc = live_ivt(c, t, tab, form, rep)) return rc;
+    } else {
+        t.m = 0;   // past IVT_MAX, or a DIR-24-8 stage: launches take the painted image
+    }
+    if (form == COP_FORM_RULE && c->n_rule_ctr)   // a new rule set counts from zero, as after cop_set_fw_table
+        HIPCHK(c, hipMemsetAsync(c->counters + RULE_OFF, 0, (size_t)c->n_rule_ctr * 8, c->stream));
+    return 0;
+}
+
+static int live_replace(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_update_report *rep_out)
+{
+    if (!c || !tab) return -EINVAL;
+    DevLpm &t = is_fw ? c->fw : c->lpm;
+    const int form = is_fw ? COP_FORM_RULE : COP_FORM_NH;
+    const uint32_t fl = c->cfg.flags;
+    cop_update_report rep;
+    memset(&rep, 0, sizeof(rep));
+    if (rep_out) *rep_out = rep;
+    HIPCHK(c, hipSetDevice(c->device));
+    // the device path paints the LDS interval and DIR-24-8 forms of a live
+    // context; a firewall stage with per-rule counters needs its counter
+    // words to cover the new table's ids already (growing them waits)
+    bool dev = (fl & COP_CFG_LIVE_TABLES) && !(fl & (is_fw ? COP_CFG_FW_BKT : (COP_CFG_LPM_TRIE | COP_CFG_LPM_BKT)));
+    if (dev && is_fw && (fl & COP_CFG_RULE_COUNTERS) &&
+        c->n_rule_ctr < std::max(tab->n_rules, std::min(tab->cfg.max_rules, COP_LPM_NH_MASK + 1u)))
+        dev = false;
+    if (!dev) {
+        if (c->pmd) return set_err(c, -EBUSY, "the replacement needs a whole-table upload (cop_pmd_stop first)");
+        const int rc = is_fw ? cop_set_fw_table(c, tab) : cop_set_route_lpm(c, tab);
+        if (rc) return rc;
+        rep.full = 1;
+        rep.h2d_bytes = ((uint64_t)4 << 24) + t.tbl8_bytes + (t.m ? (uint64_t)(2 * t.m + t.iw) * 4 : 0);
+        if (rep_out) *rep_out = rep;
+        return 0;
+    }
+    const bool want_ivt = !(fl & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24));
+    const uint32_t m_new = is_fw ? tab->n_rv : tab->report.n_intervals;
+    const bool ivt_new = want_ivt && m_new <= IVT_MAX;
+    if (c->pmd) {
+        if (is_fw && (fl & COP_CFG_RULE_COUNTERS))
+            return set_err(c, -EBUSY, "per-rule counters: replace the firewall table with the poll-mode kernel stopped");
+        // the kernel's launch geometry must stay, as for cop_update_*
+        uint32_t M = 0, ib = 0, iw = 0;
+        if (ivt_new) ivt_geometry(m_new, &M, &ib, &iw);
+        if (ivt_new != (t.m != 0) || (ivt_new && (M != t.m || iw != t.iw)))
+            return set_err(c, -EBUSY, "the replacement changes the poll-mode kernel's launch geometry (cop_pmd_stop first)");
+    }
+    PaintPlan P;
+    if (int rc = paint_plan(c, tab, form, P)) return rc;
+    const uint32_t grp_cap = live_grp_cap(tab, P.n_ext);
+    if (int rc = live_setup(c)) return rc;
+    if (int rc = paint_stage(c, P)) return rc;
+    // what is missing or outgrown, before anything is enqueued: a first tbl24,
+    // a larger tbl8, interval buffers that hold any LDS image
+    uint32_t *n24 = nullptr, *n8 = nullptr, *ns = nullptr, *nv = nullptr;
+    const size_t tbl8_need = (size_t)grp_cap * 1024;
+    const bool ivt_room = t.has_table && t.starts && t.vals;   // upload_lpm's or our own full-size pair
+    auto drop_new = [&]() {   // an error before anything is enqueued: the stage keeps what it had
+        for (void *p : {(void *)n24, (void *)n8, (void *)ns, (void *)nv})
+            if (p) c->retired.push_back({p, false});
+    };
+    hipError_t e = hipSuccess;
+    if (!t.tbl24) e = hipMalloc(&n24, (size_t)4 << 24);
+    if (e == hipSuccess && (!t.tbl8 || t.tbl8_packed || t.tbl8_bytes < tbl8_need)) e = hipMalloc(&n8, tbl8_need);
+    if (e == hipSuccess && want_ivt && !ivt_room) {
+        e = hipMalloc(&ns, (size_t)(IVT_MAX + IVT_IW_MAX) * 4);
+        if (e == hipSuccess) e = hipMalloc(&nv, (size_t)IVT_MAX * 4);
+    }
+    if (e != hipSuccess) {
+        drop_new();
+        return set_err(c, -ENOMEM, "replacement buffers: %s", hipGetErrorString(e));
+    }
+    const uint32_t groups_before = t.img ? cop_live_img_groups_used(t.img) : (t.has_table ? t.n_ext : 0u);
+    cop_live_img *book = cop_live_img_create(tab, form, grp_cap);
+    if (!book) {
+        drop_new();
+        return set_err(c, -ENOMEM, "live table book");
+    }
+    int rc = c->pmd ? pmd_pause(c) : 0;
+    if (rc) {
+        drop_new();
+        cop_live_img_free(book);
+        return rc;
+    }
+    // from here on the stage changes: launches made after this call read the new fields
+    if (n24) t.tbl24 = n24;
+    if (n8) {
+        if (t.tbl8) c->retired.push_back({t.tbl8, false});
+        t.tbl8 = n8;
+        t.tbl8_bytes = tbl8_need;
+        t.tbl8_packed = false;
+    }
+    if (ns) {
+        if (t.starts) c->retired.push_back({t.starts, false});
+        if (t.vals) c->retired.push_back({t.vals, false});
+        t.starts = ns;
+        t.vals = nv;
+    }
+    cop_live_img_free(t.img);
+    t.img = book;
+    t.tab_uid = tab->uid;
+    t.grp_cap = grp_cap;
+    t.n_ext = P.n_ext;
+    t.loaded = true;
+    t.has_table = true;
+    if (c->pmd) {
+        rc = replace_apply(c, t, tab, form, ivt_new, P, grp_cap, &rep);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "paint sync");
+        pmd_refresh_tables(c, c->pmd);
+        const int rrc = pmd_resume(c);
+        if (!rc) rc = rrc;
+    } else {
+        rc = live_order_begin(c);
+        if (!rc) rc = replace_apply(c, t, tab, form, ivt_new, P, grp_cap, &rep);
+        const int orc = live_order_end(c);
+        if (!rc) rc = orc;
+    }
+    if (rc) {
+        // the image may be painted in part: the next update or replacement starts afresh
+        cop_live_img_free(t.img);
+        t.img = nullptr;
+        return rc;
+    }
+    rep.groups_released = groups_before;
+    if (rep_out) *rep_out = rep;
+    return 0;
+}
+
+int cop_replace_fw_table(cop_ctx *c, const cop_lpm_table *t, cop_update_report *rep)
+{
+    if (c && t && t->n_rules > COP_LPM_NH_MASK) return set_err(c, -EINVAL, "rule ids exceed 24 bits");
+    return live_replace(c, true, t, rep);
+}
+
+int cop_replace_route_lpm(cop_ctx *c, const cop_lpm_table *t, cop_update_report *rep)
+{
+    return live_replace(c, false, t, rep);
 }
 
 int cop_update_fw_rules_file(cop_ctx *c, cop_lpm_table *t, const char *path, cop_update_report *rep)
@@ -3547,6 +3840,36 @@ int cop_debug_patch(cop_ctx *c, void *tbl24_dptr, uint32_t cap24, void *tbl8_dpt
     if (int rc = live_send(c, recs, n, (uint32_t *)tbl24_dptr, cap24, (uint32_t *)tbl8_dptr, cap8, &rep)) return rc;
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return (int)rep.n_records;
+}
+
+/* tests: the paint kernel alone on caller buffers (cop_internal.h) */
+int cop_debug_paint(cop_ctx *c, const uint32_t *starts, const uint32_t *entries, uint32_t niv, const uint32_t *ext24,
+                    uint32_t n_ext, void *tbl24_dptr, void *tbl8_dptr, uint32_t cap_groups)
+{
+    if (!c || !starts || !entries || (n_ext && !ext24) || !tbl24_dptr || !tbl8_dptr) return -EINVAL;
+    if (((uintptr_t)tbl24_dptr | (uintptr_t)tbl8_dptr) & 15u) return set_err(c, -EINVAL, "paint: unaligned table");
+    if (niv == 0 || niv > (1u << 28) || starts[0] != 0)
+        return set_err(c, -EINVAL, "paint: the intervals must start at address 0");
+    if (n_ext > cap_groups) return set_err(c, -EINVAL, "paint: %u extended blocks, room for %u groups", n_ext, cap_groups);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (int rc = sync_lanes(c)) return rc;
+    PaintPlan P;   // a view of the caller's arrays, released before it is destroyed
+    P.niv = niv;
+    P.n_ext = n_ext;
+    P.off_e = (niv + 3u) & ~3u;
+    P.off_x = 2 * P.off_e;
+    P.words = P.off_x + std::max((n_ext + 3u) & ~3u, 4u);
+    P.starts = const_cast<uint32_t *>(starts);
+    P.entries = const_cast<uint32_t *>(entries);
+    P.ext24 = const_cast<uint32_t *>(ext24);
+    int rc = paint_stage(c, P);
+    cop_update_report rep;
+    memset(&rep, 0, sizeof(rep));
+    if (!rc) rc = paint_send(c, P, (uint32_t *)tbl24_dptr, (uint32_t *)tbl8_dptr, cap_groups, &rep);
+    P.starts = P.entries = P.ext24 = nullptr;
+    if (rc) return rc;
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return 0;
 }
 
 /* diagnostic (not in the public header): the poll-mode kernel's phase

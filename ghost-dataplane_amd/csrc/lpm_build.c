@@ -422,6 +422,102 @@ uint32_t cop_lpm_form_n_ext(const cop_lpm_table *t, int form)
     return form == COP_FORM_RULE ? t->n_ext_rule : t->n_ext;
 }
 
+/* ---- the whole image from intervals, as the paint kernel does it ---------
+ * fill_dir24 walks the blocks with a running cursor; a GPU has no cursor, so
+ * the kernel (cop_paint.hip) and its mirror below find every entry's interval
+ * by a search, bounded by the interval range of the chunk of blocks a
+ * workgroup owns. */
+int cop_lpm_paint_plan(const cop_lpm_table *t, int form, uint32_t **starts, uint32_t **entries, uint32_t *niv,
+                       uint32_t **ext24, uint32_t *n_ext)
+{
+    if (!t || !starts || !entries || !niv || !ext24 || !n_ext) return -EINVAL;
+    *starts = *entries = *ext24 = NULL;
+    *niv = *n_ext = 0;
+    const uint32_t *st = NULL;
+    uint32_t n = 0;
+    uint32_t *e = form_entries(t, form, &st, &n);
+    if (!e) return -ENOMEM;
+    if (!n || st[0] != 0) {   /* a built table always covers [0, 2^32) */
+        free(e);
+        return -EINVAL;
+    }
+    const uint32_t ne = count_ext(st, n);
+    uint32_t *s = (uint32_t *)malloc((size_t)n * sizeof(uint32_t));
+    uint32_t *x = (uint32_t *)malloc((size_t)(ne ? ne : 1) * sizeof(uint32_t));
+    if (!s || !x) {
+        free(e);
+        free(s);
+        free(x);
+        return -ENOMEM;
+    }
+    memcpy(s, st, (size_t)n * sizeof(uint32_t));
+    uint32_t g = 0, last_blk = 0xFFFFFFFFu;
+    for (uint32_t k = 0; k < n; k++)
+        if ((st[k] & 0xFFu) != 0 && (st[k] >> 8) != last_blk) x[g++] = last_blk = st[k] >> 8;
+    *starts = s;
+    *entries = e;
+    *niv = n;
+    *ext24 = x;
+    *n_ext = g;
+    return 0;
+}
+
+/* the last k in [lo, hi] with s[k] <= x (s[lo] <= x is given) */
+static inline uint32_t paint_last_le(const uint32_t *s, uint32_t lo, uint32_t hi, uint32_t x)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo + 1) / 2;
+        if (s[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+/* the first g in [lo, hi) with x[g] >= blk (hi if none) */
+static inline uint32_t paint_rank(const uint32_t *x, uint32_t lo, uint32_t hi, uint32_t blk)
+{
+    while (lo < hi) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (x[mid] < blk) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+int cop_paint_host(const uint32_t *starts, const uint32_t *entries, uint32_t niv, const uint32_t *ext24,
+                   uint32_t n_ext, uint32_t *tbl24, uint32_t *tbl8, uint32_t cap_groups)
+{
+    if (!starts || !entries || !tbl24 || niv == 0 || starts[0] != 0 || n_ext > cap_groups) return -EINVAL;
+    if ((n_ext && !ext24) || (cap_groups && !tbl8)) return -EINVAL;
+    for (uint32_t c = 0; c < (1u << 24) / COP_PAINT_CHUNK; c++) {
+        /* workgroup c: the intervals and extended blocks of its chunk */
+        const uint32_t b0 = c * COP_PAINT_CHUNK, b1 = b0 + COP_PAINT_CHUNK - 1;
+        const uint32_t klo = paint_last_le(starts, 0, niv - 1, b0 << 8);
+        const uint32_t khi = paint_last_le(starts, klo, niv - 1, (b1 << 8) | 255u);
+        const uint32_t glo = paint_rank(ext24, 0, n_ext, b0);
+        const uint32_t ghi = paint_rank(ext24, glo, n_ext, b1 + 1);
+        for (uint32_t blk = b0; blk <= b1; blk++) {
+            const uint32_t k = paint_last_le(starts, klo, khi, blk << 8);
+            if (k < khi && starts[k + 1] <= ((blk << 8) | 255u))
+                tbl24[blk] = paint_rank(ext24, glo, ghi, blk) | COP_DIR_VALID_EXT;
+            else
+                tbl24[blk] = entries[k];
+        }
+    }
+    for (uint32_t g = 0; g < cap_groups; g++) {
+        uint32_t *grp = tbl8 + (size_t)g * 256;
+        if (g >= n_ext) {
+            memset(grp, 0, 256 * sizeof(uint32_t));
+            continue;
+        }
+        const uint32_t lo = ext24[g] << 8;
+        const uint32_t klo = paint_last_le(starts, 0, niv - 1, lo);
+        const uint32_t khi = paint_last_le(starts, klo, niv - 1, lo | 255u);
+        for (uint32_t a = 0; a < 256; a++) grp[a] = entries[paint_last_le(starts, klo, khi, lo + a)];
+    }
+    return 0;
+}
+
 uint32_t cop_lpm_form_intervals(const cop_lpm_table *t, int form, uint32_t **starts, uint32_t **entries)
 {
     if (form != COP_FORM_RULE) {

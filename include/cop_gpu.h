@@ -381,6 +381,49 @@ int  cop_update_route_lpm(cop_ctx *ctx, const cop_lpm_table *t, cop_update_repor
  * changed actions overwritten), then cop_update_fw_table. */
 int  cop_update_fw_rules_file(cop_ctx *ctx, cop_lpm_table *t, const char *path, cop_update_report *rep);
 
+/* A stage's whole table replaced in stream order. After the call returns the
+ * stage holds table t at its current generation, whatever it held before:
+ * another table, none, or the same table at any older generation (a reloaded
+ * rule set, a new routing snapshot, a table whose journal no longer reaches
+ * back). The table object must stay alive, as for cop_update_*, and a later
+ * cop_update_* of it patches incrementally.
+ *
+ * Device path: a COP_CFG_LIVE_TABLES context whose stage is in the LDS
+ * interval or the DIR-24-8 form (not COP_CFG_FW_BKT, COP_CFG_LPM_TRIE,
+ * COP_CFG_LPM_BKT) and, for a firewall table on a COP_CFG_RULE_COUNTERS
+ * context, whose per-rule counter words already cover max(rule ids of t, t's
+ * max_rules). The table's sorted intervals (about a megabyte for 100k routes)
+ * go through pinned staging and one kernel paints all of tbl24 and the tbl8
+ * groups from them where the image lives; a table of at most 8192 intervals
+ * also gets its LDS interval image copied, a larger one takes the stage to
+ * the DIR-24-8 form; every per-rule counter word of a firewall stage is
+ * zeroed, as cop_set_fw_table zeroes them. Ordering is that of cop_update_*:
+ * batches and cop_lookup_bulk calls queued before the call see the old table
+ * for every packet or address, those queued after it returns the new one, on
+ * whichever lane; no cop_sync is needed. The call does not synchronise the
+ * device, does not free device memory and does not wait for queued work (it
+ * may wait for the copy of an earlier replacement's intervals out of pinned
+ * staging). It allocates what is missing or outgrown (a first tbl24, a
+ * larger tbl8, staging); an outgrown buffer, which queued work may still
+ * read, is kept until the next cop_set_* or cop_destroy.
+ *
+ * While a poll-mode kernel serves the context: paused, painted, table
+ * parameters and pointers refreshed, relaunched; every batch is served wholly
+ * by one table. -EBUSY with the device untouched where cop_update_* refuses:
+ * a changed launch geometry (the stage's form, the LDS bytes of its interval
+ * image), a firewall table on a COP_CFG_RULE_COUNTERS context.
+ *
+ * Otherwise the call is cop_set_* (synchronous, rep->full = 1), or -EBUSY
+ * under a poll-mode kernel.
+ *
+ * Report of the device path: full 0, n_changes 0, n_records the intervals
+ * sent, tbl24_entries 1 << 24, tbl8_entries and groups_taken the new image's
+ * groups (x 256), groups_released the groups the previous image used,
+ * h2d_bytes the bytes copied. Errors as cop_update_*; after -EIO the next
+ * cop_update_* uploads the whole table. */
+int  cop_replace_fw_table(cop_ctx *ctx, const cop_lpm_table *t, cop_update_report *rep);
+int  cop_replace_route_lpm(cop_ctx *ctx, const cop_lpm_table *t, cop_update_report *rep);
+
 /* ------------------------------------------------------------------------ */
 /* Bulk lookups (rte_lpm_lookup_bulk on the device) and table audit         */
 /* ------------------------------------------------------------------------ */
