@@ -108,6 +108,19 @@ class BatchRing(Structure):
                 ("stride", c_uint32), ("data_off", c_uint32)]
 
 
+TX_MAX_FRAME = 2048   # COP_TX_MAX_FRAME
+
+
+class TxBurst(Structure):
+    _fields_ = [("frames", c_void_p), ("off", c_void_p), ("len", c_void_p), ("status", c_void_p),
+                ("cap_bytes", c_uint64), ("cap_frames", c_uint32), ("_pad", c_uint32)]
+
+
+class TxDesc(Structure):
+    _fields_ = [("lens", c_void_p), ("copy_bytes", c_uint32), ("slot_bytes", c_uint32),
+                ("out", TxBurst * MAX_DEMUX_PORTS)]
+
+
 class TraceOpts(Structure):
     _fields_ = [("n_ports", c_uint32), ("pct_non_ipv4", c_uint32), ("pct_bad_version", c_uint32),
                 ("pct_unknown_dst", c_uint32), ("pct_vport_dst", c_uint32),
@@ -157,6 +170,9 @@ SIGNATURES = {
     "cop_lookup_bulk": (c_int, [c_void_p, c_uint32, c_void_p, c_uint32, c_void_p]),
     "cop_lookup_bulk_host": (c_int, [c_void_p, c_uint32, c_void_p, c_uint64, c_void_p]),
     "cop_lookup_audit": (c_int, [c_void_p, c_uint32, c_void_p, POINTER(AuditReport), c_void_p, c_uint32]),
+    "cop_tx_gather": (c_int, [c_void_p, POINTER(Batch), POINTER(TxDesc), c_uint32]),
+    "cop_submit_tx": (c_int, [c_void_p, POINTER(Batch), POINTER(TxDesc), c_uint32]),
+    "cop_tx_gather_host": (c_int, [POINTER(Batch), POINTER(TxDesc), c_uint32, c_uint32, c_int, c_uint32]),
     "cop_rules_load_json": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
     "cop_rules_free": (None, [c_void_p]),
     "cop_rules_write_json": (c_int, [c_char_p, c_void_p, c_uint32]),
@@ -912,6 +928,21 @@ class Context:
         arr = (Batch * len(batches))(*batches)
         _check(lib().cop_submit(self.handle, arr, len(batches)), self, "submit")
 
+    def tx_gather(self, batches, tx):
+        """cop_tx_gather: the frames of the batches' forward lists (as they
+        are in device memory once everything queued so far has run) packed
+        into the tx bursts of `tx` (one TxDesc per batch, make_tx).
+        Asynchronous: valid after sync(); synchronous beside a poll-mode kernel."""
+        assert len(batches) == len(tx)
+        arr, tarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx)
+        _check(lib().cop_tx_gather(self.handle, arr, tarr, len(batches)), self, "tx_gather")
+
+    def submit_tx(self, batches, tx):
+        """cop_submit_tx: submit(batches), then their tx gather on the same lane."""
+        assert len(batches) == len(tx)
+        arr, tarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx)
+        _check(lib().cop_submit_tx(self.handle, arr, tarr, len(batches)), self, "submit_tx")
+
     def submit_ring(self, ring: BatchRing, first_slot: int, count: int):
         _check(lib().cop_submit_ring(self.handle, byref(ring), first_slot, count), self, "submit_ring")
 
@@ -1164,3 +1195,39 @@ def make_batch(pkts: DeviceBuffer | int, n: int, results: DeviceBuffer | int, st
     b.fwd_count = addr(fwd_count)
     b._keep = tuple(x for x in (pkts, offsets, results, fwd_idx, fwd_count) if isinstance(x, DeviceBuffer))
     return b
+
+
+def make_tx(out, lens=None, copy_bytes: int = 0, slot_bytes: int = 0) -> TxDesc:
+    """A batch's cop_tx_desc. out: one burst, or one per vport, each a dict
+    (or tuple in this order) of frames, off, len, status (DeviceBuffer, address
+    or None), cap_bytes, cap_frames. Slot batches give copy_bytes (slot_bytes
+    defaults to it), IMIX batches lens."""
+    def addr(x):
+        if x is None:
+            return None
+        return x.addr if isinstance(x, DeviceBuffer) else int(x)
+    t = TxDesc()
+    t.lens = addr(lens)
+    t.copy_bytes, t.slot_bytes = copy_bytes, (slot_bytes or copy_bytes)
+    bursts = out if isinstance(out, (list, tuple)) and out and isinstance(out[0], (dict, list, tuple)) else [out]
+    assert 1 <= len(bursts) <= MAX_DEMUX_PORTS
+    keep = [lens] if isinstance(lens, DeviceBuffer) else []
+    for q, b in enumerate(bursts):
+        if not isinstance(b, dict):
+            b = dict(zip(("frames", "off", "len", "status", "cap_bytes", "cap_frames"), b))
+        o = t.out[q]
+        o.frames, o.off, o.len, o.status = (addr(b.get(k)) for k in ("frames", "off", "len", "status"))
+        o.cap_bytes, o.cap_frames = int(b["cap_bytes"]), int(b["cap_frames"])
+        keep += [b.get(k) for k in ("frames", "off", "len", "status") if isinstance(b.get(k), DeviceBuffer)]
+    t._keep = tuple(keep)
+    return t
+
+
+def tx_gather_host(batches, tx, n_lists: int = 1, seg: bool = False, max_batch: int = 0) -> int:
+    """cop_tx_gather_host: the gather over host memory (every pointer in the
+    batches and descriptors a host address, e.g. ndarray.ctypes.data); the
+    list layout explicit: n_lists lists per batch, seg for segmented lists.
+    Returns the C return code (0 or -EINVAL)."""
+    assert len(batches) == len(tx)
+    arr, tarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx)
+    return lib().cop_tx_gather_host(arr, tarr, len(batches), n_lists, 1 if seg else 0, max_batch)

@@ -230,6 +230,16 @@ int cop_debug_lookup_form(cop_ctx *c, uint32_t stage);
  * (malloc-ed). 0, -EINVAL, -ENOMEM. */
 int cop_lpm_audit_probes(const cop_lpm_table *t, int form, uint32_t **ips, uint32_t *n);
 
+/* ---- tx gather (tx_gather.c, cop_tx.hip) --------------------------------- */
+/* The argument checks cop_tx_gather, cop_submit_tx and cop_tx_gather_host
+ * share (include/cop_gpu.h): n_lists lists per batch, seg != 0 for segmented
+ * lists, max_batch 0 for no limit. 0, or -EINVAL with *why (may be NULL) the
+ * reason. */
+int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t n_lists, int seg,
+                    uint32_t max_batch, const char **why);
+/* words of fwd_count a batch of n packets has in that layout */
+uint32_t cop_tx_fwd_count_words(uint32_t n, uint32_t n_lists, int seg);
+
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,
  * COP_DROPIN_STAGES (process_packet, coprocessor.c:50-65). */

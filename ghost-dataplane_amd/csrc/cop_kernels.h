@@ -239,9 +239,43 @@ struct CopKLookup {
     const uint32_t *bidx, *bpairs;
 };
 
+// cop_tx_sums / cop_tx_copy (cop_tx.hip): forwarded frames packed into tx
+// bursts (cop_tx_gather). One CopKTxList per forward list (a batch's dense
+// list, one vport's list, or a batch's segments in order), at most
+// COPK_TX_MAXL per launch; one workgroup per chunk of COPK_TX_CHUNK list
+// positions, workgroup chunk_begin + c serving the list's chunk c.
+#define COPK_TX_MAXL 32
+#define COPK_TX_CHUNK 256
+#define COPK_TX_MAX_FRAME 2048u
+struct CopKTxList {
+    const uint8_t *pkts;       // batch pkts + data_off
+    const uint32_t *offsets;   // IMIX: byte offset of packet i; slot batches: null
+    const uint32_t *lens;      // IMIX: frame length of packet i
+    const uint32_t *idx;       // the list's first index word (4-byte aligned)
+    const uint32_t *count;     // its length (dense, per vport), or one word per segment
+    uint8_t *frames;           // 16-byte aligned
+    uint32_t *off, *len;       // or null
+    uint32_t *status;          // 16-byte aligned, 4 words
+    uint32_t n;                // the batch's packets: what the list layout holds
+    uint32_t stride;
+    uint32_t copy_bytes, slot_bytes;   // slot batches
+    uint32_t cap_bytes, cap_frames;
+    uint32_t chunk_begin;      // first workgroup of this list
+    uint32_t sums_begin;       // IMIX: first word of this list's chunk byte sums in CopKTx::sums
+};
+struct CopKTx {
+    CopKTxList l[COPK_TX_MAXL];
+    uint32_t *sums;            // IMIX: context-owned scratch, one word per chunk
+    uint32_t nl;
+    uint32_t nchunks;          // the grid
+    uint32_t seg;              // lists are segmented (COP_CFG_SEG_LISTS)
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// imix: every list is of an IMIX batch (the byte-sum pre-pass runs first), or none is
+hipError_t copk_tx_launch(const CopKTx *p, int imix, hipStream_t stream);
 // form: COPK_TBL_*; the grid is min(tiles, ncu x resident workgroups per CU,
 // grid_cap if non-zero)
 hipError_t copk_lookup_launch(const CopKLookup *p, int form, uint32_t ncu, uint32_t grid_cap, hipStream_t stream);

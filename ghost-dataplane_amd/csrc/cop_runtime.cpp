@@ -382,6 +382,10 @@ struct cop_ctx {
     };
     std::vector<Retired> retired;
     LookupStage lookup_stage[2];       // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
+    // cop_tx_gather / cop_submit_tx: per lane, the IMIX chunk byte sums (allocated at the lane's
+    // first IMIX gather, at the context's worst case) and the event that orders a gather behind the lane
+    uint32_t *tx_sums[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t tx_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -564,6 +568,10 @@ void cop_destroy(cop_ctx *c)
         if (S.done) (void)hipEventDestroy(S.done);
     }
     if (c->live_done) (void)hipEventDestroy(c->live_done);
+    for (auto &p : c->tx_sums)
+        if (p) (void)hipFree(p);
+    for (auto &e : c->tx_ev)
+        if (e) (void)hipEventDestroy(e);
     free_retired(c);
     if (c->paint_h) (void)hipHostFree(c->paint_h);
     if (c->paint_d) (void)hipFree(c->paint_d);
@@ -3820,6 +3828,137 @@ int cop_lookup_audit(cop_ctx *c, uint32_t stage, const cop_lpm_table *tab, cop_a
     free(dev);
     free(host);
     return rc;
+}
+
+// ---- tx gather (cop_tx.hip) -------------------------------------------------
+// cop_tx_gather / cop_submit_tx: every forward list of the batches becomes one
+// CopKTxList; a launch carries up to COPK_TX_MAXL of them (its parameters are
+// kernel arguments, so nothing the host could rewrite under queued work), all
+// of one kind (slot or IMIX). IMIX launches use the lane's chunk-sum scratch,
+// allocated once at the worst case the context admits (max_batches x
+// ceil(max_batch / 256) x lists per batch words) and freed by cop_destroy
+// alone: launches of one lane run in order, so the next gather's pre-pass
+// overwrites the sums only after this one's copy kernel has read them.
+static int tx_layout(cop_ctx *c, uint32_t *n_lists, int *seg)
+{
+    if (c->cfg.flags & COP_CFG_NO_COMPACT)
+        return set_err(c, -EINVAL, "tx gather: a COP_CFG_NO_COMPACT context builds no forward lists");
+    *seg = (c->cfg.flags & COP_CFG_SEG_LISTS) != 0;
+    *n_lists = (c->cfg.flags & COP_CFG_DEMUX_PORTS) ? c->cfg.n_ports : 1u;
+    return 0;
+}
+
+static int tx_check(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t *n_lists,
+                    int *seg)
+{
+    if (int rc = tx_layout(c, n_lists, seg)) return rc;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "tx gather: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_tx_validate(batches, tx, nb, *n_lists, *seg, c->cfg.max_batch, &why))
+        return set_err(c, rc, "tx gather: %s", why);
+    return 0;
+}
+
+static int tx_launch(cop_ctx *c, int lane, hipStream_t s, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb,
+                     uint32_t n_lists, int seg)
+{
+    const uint32_t cpb = (c->cfg.max_batch + COPK_TX_CHUNK - 1) / COPK_TX_CHUNK;
+    const size_t sums_words = (size_t)c->cfg.max_batches * cpb * n_lists;
+    CopKTx p;
+    memset(&p, 0, sizeof(p));
+    p.seg = seg ? 1u : 0u;
+    int kind = -1;          // of the lists in p: 0 slot, 1 IMIX
+    uint32_t sums_used = 0;
+    auto flush = [&]() -> int {
+        if (!p.nl) return 0;
+        const hipError_t e = copk_tx_launch(&p, kind, s);
+        p.nl = 0;
+        p.nchunks = 0;
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "tx gather launch: %s", hipGetErrorString(e));
+    };
+    for (uint32_t i = 0; i < nb; i++) {
+        const cop_batch &b = batches[i];
+        const cop_tx_desc &t = tx[i];
+        const int imix = b.offsets != nullptr;
+        if (imix && !c->tx_sums[lane]) {
+            HIPCHK(c, hipMalloc(&c->tx_sums[lane], sums_words * 4));
+        }
+        const uint32_t chunks = b.n ? (b.n + COPK_TX_CHUNK - 1) / COPK_TX_CHUNK : 1u;
+        for (uint32_t q = 0; q < n_lists; q++) {
+            if (p.nl == COPK_TX_MAXL || (p.nl && kind != imix))
+                if (int rc = flush()) return rc;
+            kind = imix;
+            const cop_tx_burst &o = t.out[q];
+            CopKTxList &l = p.l[p.nl++];
+            l.pkts = (const uint8_t *)b.pkts + b.data_off;
+            l.offsets = b.offsets;
+            l.lens = t.lens;
+            l.idx = b.n ? b.fwd_idx + (size_t)q * b.n : nullptr;
+            l.count = b.n ? b.fwd_count + q : nullptr;
+            l.frames = (uint8_t *)o.frames;
+            l.off = o.off;
+            l.len = o.len;
+            l.status = o.status;
+            l.n = b.n;
+            l.stride = b.stride;
+            l.copy_bytes = t.copy_bytes;
+            l.slot_bytes = t.slot_bytes;
+            l.cap_bytes = (uint32_t)o.cap_bytes;
+            l.cap_frames = o.cap_frames;
+            l.chunk_begin = p.nchunks;
+            l.sums_begin = sums_used;
+            p.nchunks += chunks;
+            if (imix) sums_used += chunks;   // <= sums_words: nb <= max_batches, n <= max_batch
+            p.sums = c->tx_sums[lane];
+        }
+    }
+    return flush();
+}
+
+int cop_tx_gather(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = tx_check(c, batches, tx, nb, &n_lists, &seg)) return rc;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->pmd) {
+        // as cop_lookup_bulk: pause the poll-mode kernel, gather on the free GPU, relaunch it
+        if (int rc = pmd_pause(c)) return rc;
+        int rc = tx_launch(c, 0, c->stream, batches, tx, nb, n_lists, seg);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "tx gather sync");
+        const int rrc = pmd_resume(c);
+        return rc ? rc : rrc;
+    }
+    const int lane = c->next_lane;
+    Lane &L = c->lane[lane];
+    c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    // behind everything queued so far on every other lane (live_order_begin's event pattern);
+    // a lane with nothing in flight has nothing to be ordered behind
+    for (int l = 0; l < c->n_lanes; l++) {
+        if (l == lane || hipStreamQuery(c->lane[l].s) == hipSuccess) continue;
+        if (!c->tx_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->tx_ev[l], hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->tx_ev[l], c->lane[l].s));
+        HIPCHK(c, hipStreamWaitEvent(L.s, c->tx_ev[l], 0));
+    }
+    (void)hipGetLastError();   // a busy lane's hipErrorNotReady is no launch error
+    return tx_launch(c, lane, L.s, batches, tx, nb, n_lists, seg);
+}
+
+int cop_submit_tx(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (c->pmd) return set_err(c, -EBUSY, "submit_tx: a poll-mode kernel serves the context");
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = tx_check(c, batches, tx, nb, &n_lists, &seg)) return rc;
+    const int lane = c->next_lane;
+    Lane &L = c->lane[lane];
+    c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    if (int rc = submit_on(c, L, batches, nb, true, c->cfg.stages)) return rc;
+    return tx_launch(c, lane, L.s, batches, tx, nb, n_lists, seg);
 }
 
 /* tests: the patch kernel alone on caller buffers (cop_internal.h) */

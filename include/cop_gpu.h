@@ -574,6 +574,88 @@ int  cop_sync(cop_ctx *ctx);
 /* Non-blocking: 0 when idle, -EAGAIN while work is in flight. */
 int  cop_poll(cop_ctx *ctx);
 
+/* ------------------------------------------------------------------------ */
+/* Tx gather: forwarded frames packed into tx bursts on the device          */
+/* ------------------------------------------------------------------------ */
+
+/* The tx half of coprocessor() (switch.c:464-473) for batches resident in
+ * device memory: the frames of a batch's forward list are copied, in list
+ * order, into a contiguous tx burst, and what does not fit is counted as the
+ * reference counts tx_dropped. One burst per forward list: out[0], or on a
+ * COP_CFG_DEMUX_PORTS context out[q] for vport q (q < n_ports).
+ *
+ * Lists: the layout public submits on this context write: one dense list per
+ * batch; with COP_CFG_DEMUX_PORTS one per vport at fwd_idx + q*n, its length
+ * at fwd_count[q]; with COP_CFG_SEG_LISTS the concatenation of the batch's
+ * COP_SEG_PKTS-packet segments in order. A list's length is clamped to what
+ * the layout holds (n; a segment's packet count), an index to n - 1. A ring
+ * slot is passed as a cop_batch whose pointers the caller computes.
+ *
+ * Per list L = (i_0, i_1, ...), packet i's source where cop_batch puts it:
+ *   slot batch (offsets == NULL): ext_k = len_k = copy_bytes,
+ *                                 off_k = k * slot_bytes;
+ *   IMIX batch:  l = clamp(lens[i_k], 1, COP_TX_MAX_FRAME), len_k = l,
+ *                ext_k = (l + 15) & ~15, off_k = the sum of the earlier ext;
+ *                the caller guarantees ext_k readable bytes at the packet.
+ * Frame k is written iff k < cap_frames and off_k + ext_k <= cap_bytes; the
+ * offsets are monotone, so the written frames are a prefix of W frames.
+ * frames[off_k .. off_k + ext_k) holds the source's ext_k bytes; off[k] and
+ * len[k] (when not NULL) are written for k < W; status = {W, bytes used
+ * (off_{W-1} + ext_{W-1}, or 0), |L| - W, 0}. Nothing else is written: not the
+ * gap between slot frames, not a byte past the used bytes, not off / len at
+ * k >= W, no word of the batch, its lists or its records. No counter is
+ * touched. A batch with n == 0 writes a zero status. */
+#define COP_TX_MAX_FRAME 2048u
+typedef struct cop_tx_burst {
+    void     *frames;    /* device, 16-byte aligned */
+    uint32_t *off;       /* device or NULL: off[k] = byte offset of frame k in frames */
+    uint32_t *len;       /* device or NULL: len[k] = its length */
+    uint32_t *status;    /* device, 16-byte aligned, 4 words: frames written, bytes used,
+                            frames dropped (forwarded but did not fit), 0 */
+    uint64_t  cap_bytes; /* < 2^32 */
+    uint32_t  cap_frames;
+    uint32_t  _pad;
+} cop_tx_burst;
+typedef struct cop_tx_desc {       /* per batch */
+    const uint32_t *lens; /* IMIX batches (offsets != NULL): device, n words, frame length of
+                             packet i, 1..COP_TX_MAX_FRAME; slot batches: NULL */
+    uint32_t copy_bytes;  /* slot batches: bytes copied per frame, multiple of 16,
+                             16 .. min(stride - data_off, COP_TX_MAX_FRAME); IMIX: 0 */
+    uint32_t slot_bytes;  /* slot batches: bytes between output frames, multiple of 16,
+                             >= copy_bytes; IMIX: 0 */
+    cop_tx_burst out[COP_MAX_DEMUX_PORTS];
+} cop_tx_desc;
+
+/* Gather lists that exist already or are queued already (an earlier
+ * cop_submit / cop_submit_ring on any lane, slots a poll-mode kernel has
+ * completed). Asynchronous, on the next launch lane, ordered behind everything
+ * queued before it on every lane; the outputs are valid after cop_sync. While
+ * a poll-mode kernel serves the context the call is synchronous, as
+ * cop_lookup_bulk is: the kernel is paused, the gather runs on the free GPU,
+ * the kernel is relaunched; the outputs are valid on return.
+ * nb == 0 returns 0 and launches nothing. -EINVAL (nothing launched, nothing
+ * written): nb > max_batches; n > max_batch; n > 0 without pkts, fwd_idx or
+ * fwd_count; a COP_CFG_NO_COMPACT context; packet starts not 16-byte aligned
+ * (pkts, data_off, a stride that is no multiple of 16: 12-byte records); bad
+ * copy_bytes / slot_bytes; an IMIX batch without lens, or lens / non-zero
+ * copy_bytes / slot_bytes on the wrong kind; frames or status NULL or not
+ * 16-byte aligned; cap_bytes >= 2^32; n * COP_TX_MAX_FRAME >= 2^32; an output
+ * extent (frames, off, len, status) that overlaps any batch's packets
+ * (slot batches: n * stride bytes), offsets, lens, records or lists. */
+int  cop_tx_gather(cop_ctx *ctx, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb);
+/* cop_submit of the batches followed by their gather, on the same lane: one
+ * call, no sync in between. -EBUSY while a poll-mode kernel serves the
+ * context; cop_tx_gather's and cop_submit's errors otherwise, checked before
+ * anything is queued. */
+int  cop_submit_tx(cop_ctx *ctx, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb);
+/* The same function over host memory (every pointer a host pointer): the
+ * kernel's mirror. The list layout is given explicitly: n_lists lists per
+ * batch (1, or the vports of a demux layout, <= COP_MAX_DEMUX_PORTS), seg != 0
+ * for segmented lists (n_lists must be 1). max_batch 0: no limit on n.
+ * 0 or -EINVAL as above. */
+int  cop_tx_gather_host(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t n_lists,
+                        int seg, uint32_t max_batch);
+
 /* End-to-end path from host memory (NIC/KNI mbuf data): gather the first 64
  * bytes of each packet into pinned staging, hipMemcpyAsync H2D, run the
  * pipeline, hipMemcpyAsync D2H of results and forward list. Synchronous. */
