@@ -121,6 +121,19 @@ class TxDesc(Structure):
                 ("out", TxBurst * MAX_DEMUX_PORTS)]
 
 
+SKETCH_MAX_ROWS = 4    # COP_SKETCH_MAX_ROWS
+SKETCH_KEY_SRC, SKETCH_KEY_DST = 0, 1
+
+
+class SketchConfig(Structure):
+    _fields_ = [("rows", c_uint32), ("log2_cols", c_uint32), ("key", c_uint32), ("key_depth", c_uint32),
+                ("seed", c_uint64)]
+
+
+class PoliceDesc(Structure):
+    _fields_ = [("threshold", c_uint64), ("out_idx", c_void_p), ("out_count", c_void_p), ("status", c_void_p)]
+
+
 class TraceOpts(Structure):
     _fields_ = [("n_ports", c_uint32), ("pct_non_ipv4", c_uint32), ("pct_bad_version", c_uint32),
                 ("pct_unknown_dst", c_uint32), ("pct_vport_dst", c_uint32),
@@ -173,6 +186,19 @@ SIGNATURES = {
     "cop_tx_gather": (c_int, [c_void_p, POINTER(Batch), POINTER(TxDesc), c_uint32]),
     "cop_submit_tx": (c_int, [c_void_p, POINTER(Batch), POINTER(TxDesc), c_uint32]),
     "cop_tx_gather_host": (c_int, [POINTER(Batch), POINTER(TxDesc), c_uint32, c_uint32, c_int, c_uint32]),
+    "cop_sketch_create": (c_int, [c_void_p, POINTER(SketchConfig), POINTER(c_void_p)]),
+    "cop_sketch_destroy": (c_int, [c_void_p, c_void_p]),
+    "cop_sketch_update": (c_int, [c_void_p, c_void_p, POINTER(Batch), c_uint32, c_uint32]),
+    "cop_sketch_query": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_void_p]),
+    "cop_sketch_police": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(PoliceDesc), c_uint32]),
+    "cop_sketch_decay": (c_int, [c_void_p, c_void_p, c_uint32]),
+    "cop_sketch_read": (c_int, [c_void_p, c_void_p, c_void_p, c_uint64]),
+    "cop_sketch_device_ptr": (c_int, [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_uint64)]),
+    "cop_sketch_params": (c_int, [POINTER(SketchConfig), POINTER(c_uint32), POINTER(c_uint32)]),
+    "cop_sketch_update_host": (c_int, [POINTER(SketchConfig), c_void_p, POINTER(Batch), c_uint32, c_uint32, c_uint32]),
+    "cop_sketch_query_host": (c_int, [POINTER(SketchConfig), c_void_p, c_void_p, c_uint32, c_void_p]),
+    "cop_sketch_police_host": (c_int, [POINTER(SketchConfig), c_void_p, POINTER(Batch), POINTER(PoliceDesc), c_uint32,
+                                       c_uint32, c_int, c_uint32]),
     "cop_rules_load_json": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
     "cop_rules_free": (None, [c_void_p]),
     "cop_rules_write_json": (c_int, [c_char_p, c_void_p, c_uint32]),
@@ -943,6 +969,11 @@ class Context:
         arr, tarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx)
         _check(lib().cop_submit_tx(self.handle, arr, tarr, len(batches)), self, "submit_tx")
 
+    def sketch(self, rows: int = 4, log2_cols: int = 14, key: int = SKETCH_KEY_SRC, key_depth: int = 32,
+               seed: int = 0) -> "Sketch":
+        """cop_sketch_create: a count-min sketch of rows << log2_cols u64 counters on this context."""
+        return Sketch(self, sketch_config(rows, log2_cols, key, key_depth, seed))
+
     def submit_ring(self, ring: BatchRing, first_slot: int, count: int):
         _check(lib().cop_submit_ring(self.handle, byref(ring), first_slot, count), self, "submit_ring")
 
@@ -1195,6 +1226,99 @@ def make_batch(pkts: DeviceBuffer | int, n: int, results: DeviceBuffer | int, st
     b.fwd_count = addr(fwd_count)
     b._keep = tuple(x for x in (pkts, offsets, results, fwd_idx, fwd_count) if isinstance(x, DeviceBuffer))
     return b
+
+
+def sketch_config(rows: int = 4, log2_cols: int = 14, key: int = SKETCH_KEY_SRC, key_depth: int = 32,
+                  seed: int = 0) -> SketchConfig:
+    cfg = SketchConfig()
+    cfg.rows, cfg.log2_cols, cfg.key, cfg.key_depth, cfg.seed = rows, log2_cols, key, key_depth, seed
+    return cfg
+
+
+class Sketch:
+    """A context's count-min sketch (cop_sketch_*). Every call but read() is
+    asynchronous (valid after ctx.sync()); synchronous beside a poll-mode kernel."""
+
+    def __init__(self, ctx: "Context", cfg: SketchConfig):
+        self.ctx, self.cfg, self.handle = ctx, cfg, c_void_p()
+        _check(lib().cop_sketch_create(ctx.handle, byref(cfg), byref(self.handle)), ctx, "sketch_create")
+        self.words = cfg.rows << cfg.log2_cols
+
+    def destroy(self):
+        if self.handle:
+            h, self.handle = self.handle, c_void_p()
+            _check(lib().cop_sketch_destroy(self.ctx.handle, h), self.ctx, "sketch_destroy")
+
+    def update(self, batches, verdict_mask: int = 0):
+        arr = (Batch * len(batches))(*batches)
+        _check(lib().cop_sketch_update(self.ctx.handle, self.handle, arr, len(batches), verdict_mask), self.ctx,
+               "sketch_update")
+
+    def query(self, ips, n: int, out):
+        """ips: n u32 device words, out: n u64 device words (DeviceBuffer or address)."""
+        a = lambda x: x.addr if isinstance(x, DeviceBuffer) else x
+        _check(lib().cop_sketch_query(self.ctx.handle, self.handle, a(ips), n, a(out)), self.ctx, "sketch_query")
+
+    def police(self, batches, pol):
+        assert len(batches) == len(pol)
+        arr, parr = (Batch * len(batches))(*batches), (PoliceDesc * len(pol))(*pol)
+        _check(lib().cop_sketch_police(self.ctx.handle, self.handle, arr, parr, len(batches)), self.ctx,
+               "sketch_police")
+
+    def decay(self, shift: int):
+        _check(lib().cop_sketch_decay(self.ctx.handle, self.handle, shift), self.ctx, "sketch_decay")
+
+    def read(self, cap_words: int | None = None) -> np.ndarray:
+        """cop_sketch_read: the counters, rows x cols (synchronous)."""
+        cap = self.words if cap_words is None else cap_words
+        out = np.zeros(max(cap, 1), dtype=np.uint64)
+        rc = lib().cop_sketch_read(self.ctx.handle, self.handle, out.ctypes.data, cap)
+        if rc < 0:
+            _check(rc, self.ctx, "sketch_read")
+        return out[:rc].reshape(self.cfg.rows, -1)
+
+    def device_ptr(self):
+        """(device address of the counters, words)."""
+        p, w = c_void_p(), c_uint64()
+        _check(lib().cop_sketch_device_ptr(self.ctx.handle, self.handle, byref(p), byref(w)), self.ctx,
+               "sketch_device_ptr")
+        return p.value, w.value
+
+
+def make_police(threshold: int, out_idx, out_count, status) -> PoliceDesc:
+    """A batch's cop_police_desc (DeviceBuffer, address or None each)."""
+    a = lambda x: x.addr if isinstance(x, DeviceBuffer) else x
+    p = PoliceDesc()
+    p.threshold, p.out_idx, p.out_count, p.status = threshold, a(out_idx), a(out_count), a(status)
+    p._keep = tuple(x for x in (out_idx, out_count, status) if isinstance(x, DeviceBuffer))
+    return p
+
+
+def sketch_params(cfg: SketchConfig):
+    """cop_sketch_params: (a, b), 4 u32 each; None on -EINVAL."""
+    a, b = (c_uint32 * 4)(), (c_uint32 * 4)()
+    if lib().cop_sketch_params(byref(cfg), a, b):
+        return None
+    return np.array(a[:], dtype=np.uint32), np.array(b[:], dtype=np.uint32)
+
+
+def sketch_update_host(cfg: SketchConfig, counters: np.ndarray, batches, verdict_mask: int = 0, max_batch: int = 0) -> int:
+    """cop_sketch_update_host over host memory (every pointer a host address). Returns the C code."""
+    arr = (Batch * len(batches))(*batches)
+    return lib().cop_sketch_update_host(byref(cfg), counters.ctypes.data, arr, len(batches), verdict_mask, max_batch)
+
+
+def sketch_query_host(cfg: SketchConfig, counters: np.ndarray, ips: np.ndarray, out: np.ndarray, n=None) -> int:
+    return lib().cop_sketch_query_host(byref(cfg), counters.ctypes.data, ips.ctypes.data,
+                                       len(ips) if n is None else n, out.ctypes.data)
+
+
+def sketch_police_host(cfg: SketchConfig, counters: np.ndarray, batches, pol, n_lists: int = 1, seg: bool = False,
+                       max_batch: int = 0) -> int:
+    assert len(batches) == len(pol)
+    arr, parr = (Batch * len(batches))(*batches), (PoliceDesc * len(pol))(*pol)
+    return lib().cop_sketch_police_host(byref(cfg), counters.ctypes.data, arr, parr, len(batches), n_lists,
+                                        1 if seg else 0, max_batch)
 
 
 def make_tx(out, lens=None, copy_bytes: int = 0, slot_bytes: int = 0) -> TxDesc:

@@ -240,6 +240,19 @@ int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb
 /* words of fwd_count a batch of n packets has in that layout */
 uint32_t cop_tx_fwd_count_words(uint32_t n, uint32_t n_lists, int seg);
 
+/* ---- sketch (sketch.c, cop_sketch.hip) ------------------------------------- */
+/* The argument checks the cop_sketch_* device entry points and the host mirror
+ * share (include/cop_gpu.h "Sketch"). 0, or -EINVAL with *why (may be NULL)
+ * the reason. */
+int cop_sketch_config_check(const cop_sketch_config *cfg, const char **why);
+int cop_sketch_update_validate(const cop_batch *batches, uint32_t nb, uint32_t verdict_mask, uint32_t max_batch,
+                               const char **why);
+int cop_sketch_query_validate(const cop_sketch_config *cfg, const void *counters, const uint32_t *ips, uint32_t n,
+                              const uint64_t *out, const char **why);
+int cop_sketch_police_validate(const cop_sketch_config *cfg, const void *counters, const cop_batch *batches,
+                               const cop_police_desc *pol, uint32_t nb, uint32_t n_lists, int seg,
+                               uint32_t max_batch, const char **why);
+
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,
  * COP_DROPIN_STAGES (process_packet, coprocessor.c:50-65). */

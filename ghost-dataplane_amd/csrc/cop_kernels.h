@@ -271,9 +271,71 @@ struct CopKTx {
     uint32_t seg;              // lists are segmented (COP_CFG_SEG_LISTS)
 };
 
+// cop_sketch_* (cop_sketch.hip): a count-min sketch of u64 counters in device
+// memory (cop_sketch_update / query / police / decay).
+#define COPK_SK_MAXB 32          /* batches per update launch */
+#define COPK_SK_MAXL 32          /* forward lists per police launch */
+#define COPK_SK_CHUNK 256        /* packets (update) / list positions (police) per workgroup */
+#define COPK_SK_SCRATCH_WORDS 16 /* police scratch per chunk: 4 x u64 keep ballots (one per wave), kept, cnt, pad */
+struct CopKSketch {
+    unsigned long long *ctr;   // rows << log2_cols words
+    uint32_t a[4], b[4];       // col_r(k) = (k * a[r] + b[r]) >> col_shift
+    uint32_t rows;
+    uint32_t log2_cols;
+    uint32_t col_shift;        // 32 - log2_cols
+    uint32_t key_shift;        // 32 - key_depth
+    uint32_t dst;              // key on the destination address
+};
+struct CopKSkBatch {
+    const uint8_t *pkts;       // batch pkts + data_off
+    const uint32_t *offsets;   // IMIX: byte offset of packet i; else null
+    const void *results;       // 8-byte records (update with a verdict mask) or null
+    uint32_t n;
+    uint32_t stride;           // 16: COP_HDR16_STRIDE records
+    uint32_t chunk_begin;      // first workgroup of this batch
+    uint32_t _pad;
+};
+struct CopKSkUpdate {
+    CopKSketch sk;
+    CopKSkBatch b[COPK_SK_MAXB];
+    uint32_t nb;
+    uint32_t nchunks;          // the grid
+    uint32_t verdict_mask;
+    uint32_t combine;          // equal keys of a workgroup combined in LDS before going to memory (0: timing A/B only)
+};
+struct CopKSkList {
+    const uint8_t *pkts;       // batch pkts + data_off
+    const uint32_t *offsets;
+    const uint32_t *idx;       // the list's first index word
+    const uint32_t *count;     // its length (dense, per vport), or one word per segment
+    uint32_t *out_idx;         // the same position of the output layout
+    uint32_t *out_count;
+    uint32_t *status;          // 16-byte aligned, 4 words
+    unsigned long long threshold;
+    uint32_t n;
+    uint32_t stride;
+    uint32_t chunk_begin;      // first workgroup of this list; its scratch at (chunk_begin + c) * COPK_SK_SCRATCH_WORDS
+    uint32_t _pad;
+};
+struct CopKSkPolice {
+    CopKSketch sk;
+    CopKSkList l[COPK_SK_MAXL];
+    uint32_t *scratch;         // context-owned, nchunks * COPK_SK_SCRATCH_WORDS words from scratch_begin
+    uint32_t scratch_begin;    // in chunks
+    uint32_t nl;
+    uint32_t nchunks;          // the grid
+    uint32_t seg;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+hipError_t copk_sketch_update_launch(const CopKSkUpdate *p, hipStream_t stream);
+hipError_t copk_sketch_police_launch(const CopKSkPolice *p, hipStream_t stream);
+hipError_t copk_sketch_query_launch(const CopKSketch *sk, const uint32_t *ips, uint32_t n, unsigned long long *out,
+                                    hipStream_t stream);
+// every counter >>= shift (1..63), or 0 (64)
+hipError_t copk_sketch_decay_launch(const CopKSketch *sk, uint32_t shift, hipStream_t stream);
 // imix: every list is of an IMIX batch (the byte-sum pre-pass runs first), or none is
 hipError_t copk_tx_launch(const CopKTx *p, int imix, hipStream_t stream);
 // form: COPK_TBL_*; the grid is min(tiles, ncu x resident workgroups per CU,

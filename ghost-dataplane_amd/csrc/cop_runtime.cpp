@@ -21,6 +21,7 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <functional>
 #include <mutex>
 #include <thread>
 #include <vector>
@@ -386,6 +387,10 @@ struct cop_ctx {
     // first IMIX gather, at the context's worst case) and the event that orders a gather behind the lane
     uint32_t *tx_sums[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t tx_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    // cop_sketch_*: the context's sketches, and per lane the police scratch (allocated at the
+    // lane's first police, at the context's worst case)
+    std::vector<cop_sketch *> sketches;
+    uint32_t *pol_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -499,6 +504,8 @@ static void free_retired(cop_ctx *c)
 
 static void coll_destroy(cop_ctx *c);
 
+static void sketch_free_all(cop_ctx *c);
+
 void cop_destroy(cop_ctx *c)
 {
     if (!c) return;
@@ -572,6 +579,7 @@ void cop_destroy(cop_ctx *c)
         if (p) (void)hipFree(p);
     for (auto &e : c->tx_ev)
         if (e) (void)hipEventDestroy(e);
+    sketch_free_all(c);
     free_retired(c);
     if (c->paint_h) (void)hipHostFree(c->paint_h);
     if (c->paint_d) (void)hipFree(c->paint_d);
@@ -3959,6 +3967,272 @@ int cop_submit_tx(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, u
     c->next_lane = (c->next_lane + 1) % c->n_lanes;
     if (int rc = submit_on(c, L, batches, nb, true, c->cfg.stages)) return rc;
     return tx_launch(c, lane, L.s, batches, tx, nb, n_lists, seg);
+}
+
+// ---- sketch (cop_sketch.hip) ------------------------------------------------
+// A sketch is its configuration, the hash parameters derived from it (so host
+// and device agree bit for bit) and rows << log2_cols u64 words of device
+// memory. The launch parameters are kernel arguments, so nothing the host
+// could rewrite under queued work. Ordering is cop_tx_gather's: the next
+// launch lane, behind every busy lane by events; beside a poll-mode kernel
+// pause, run on the side stream, sync, resume.
+struct cop_sketch {
+    cop_ctx *owner;
+    cop_sketch_config cfg;
+    CopKSketch k;
+    uint64_t words;
+};
+
+static void sketch_free_all(cop_ctx *c)
+{
+    for (cop_sketch *s : c->sketches) {
+        if (s->k.ctr) (void)hipFree(s->k.ctr);
+        delete s;
+    }
+    c->sketches.clear();
+    for (auto &p : c->pol_scratch) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+}
+
+static int sketch_of(cop_ctx *c, const cop_sketch *sk, const char *what)
+{
+    if (!sk || std::find(c->sketches.begin(), c->sketches.end(), sk) == c->sketches.end())
+        return set_err(c, -EINVAL, "%s: not a sketch of this context", what);
+    return 0;
+}
+
+// Runs launch(lane, stream) as a side call: asynchronous on the next lane behind every lane's queued
+// work, or synchronous between pmd_pause and pmd_resume on the side stream.
+static int sketch_run(cop_ctx *c, const char *what, const std::function<int(int, hipStream_t)> &launch)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->pmd) {
+        if (int rc = pmd_pause(c)) return rc;
+        int rc = launch(0, c->stream);
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s sync", what);
+        const int rrc = pmd_resume(c);
+        return rc ? rc : rrc;
+    }
+    const int lane = c->next_lane;
+    Lane &L = c->lane[lane];
+    c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    // live_order_begin's event pattern; a lane with nothing in flight has nothing to be ordered behind
+    for (int l = 0; l < c->n_lanes; l++) {
+        if (l == lane || hipStreamQuery(c->lane[l].s) == hipSuccess) continue;
+        if (!c->tx_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->tx_ev[l], hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->tx_ev[l], c->lane[l].s));
+        HIPCHK(c, hipStreamWaitEvent(L.s, c->tx_ev[l], 0));
+    }
+    (void)hipGetLastError();   // a busy lane's hipErrorNotReady is no launch error
+    return launch(lane, L.s);
+}
+
+int cop_sketch_create(cop_ctx *c, const cop_sketch_config *cfg, cop_sketch **out)
+{
+    if (!c || !out) return -EINVAL;
+    const char *why = "";
+    if (cop_sketch_config_check(cfg, &why)) return set_err(c, -EINVAL, "sketch: %s", why);
+    HIPCHK(c, hipSetDevice(c->device));
+    cop_sketch *s = new cop_sketch();
+    s->owner = c;
+    s->cfg = *cfg;
+    s->words = (uint64_t)cfg->rows << cfg->log2_cols;
+    memset(&s->k, 0, sizeof(s->k));
+    (void)cop_sketch_params(cfg, s->k.a, s->k.b);
+    s->k.rows = cfg->rows;
+    s->k.log2_cols = cfg->log2_cols;
+    s->k.col_shift = 32u - cfg->log2_cols;
+    s->k.key_shift = 32u - cfg->key_depth;
+    s->k.dst = cfg->key == COP_SKETCH_KEY_DST;
+    // the allocation and the zeroing are synchronous and touch nothing queued work uses; a
+    // poll-mode kernel is paused for them as for every sketch call
+    if (int rc = pmd_pause(c)) {
+        delete s;
+        return rc;
+    }
+    int rc = 0;
+    if (hipMalloc(&s->k.ctr, s->words * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        s->k.ctr = nullptr;
+        rc = set_err(c, -ENOMEM, "sketch: %llu counter bytes", (unsigned long long)s->words * 8);
+    } else if (hipMemsetAsync(s->k.ctr, 0, s->words * 8, c->stream) != hipSuccess ||
+               hipStreamSynchronize(c->stream) != hipSuccess) {
+        rc = set_err(c, -EIO, "sketch: zeroing the counters");
+    }
+    const int rrc = pmd_resume(c);
+    if (rc || rrc) {
+        if (s->k.ctr) (void)hipFree(s->k.ctr);
+        delete s;
+        return rc ? rc : rrc;
+    }
+    c->sketches.push_back(s);
+    *out = s;
+    return 0;
+}
+
+int cop_sketch_destroy(cop_ctx *c, cop_sketch *sk)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_destroy")) return rc;
+    if (int rc = sync_lanes(c)) return rc;   // queued work may use the counters
+    // beside a poll-mode kernel every sketch call has completed on return, and hipFree must not wait for it
+    if (int rc = pmd_pause(c)) return rc;
+    (void)hipFree(sk->k.ctr);
+    const int rrc = pmd_resume(c);
+    c->sketches.erase(std::find(c->sketches.begin(), c->sketches.end(), sk));
+    delete sk;
+    return rrc;
+}
+
+int cop_sketch_update(cop_ctx *c, cop_sketch *sk, const cop_batch *batches, uint32_t nb, uint32_t verdict_mask)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_update")) return rc;
+    if (nb == 0) return 0;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "sketch_update: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_sketch_update_validate(batches, nb, verdict_mask, c->cfg.max_batch, &why))
+        return set_err(c, rc, "sketch_update: %s", why);
+    static const bool combine = !(getenv("COP_SKETCH_COMBINE") && !strcmp(getenv("COP_SKETCH_COMBINE"), "0"));
+    return sketch_run(c, "sketch_update", [&](int, hipStream_t s) -> int {
+        CopKSkUpdate p;
+        memset(&p, 0, sizeof(p));
+        p.sk = sk->k;
+        p.verdict_mask = verdict_mask;
+        p.combine = combine ? 1u : 0u;
+        auto flush = [&]() -> int {
+            const hipError_t e = copk_sketch_update_launch(&p, s);
+            p.nb = 0;
+            p.nchunks = 0;
+            return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_update launch: %s", hipGetErrorString(e));
+        };
+        for (uint32_t i = 0; i < nb; i++) {
+            const cop_batch &b = batches[i];
+            if (!b.n) continue;
+            if (p.nb == COPK_SK_MAXB)
+                if (int rc = flush()) return rc;
+            CopKSkBatch &k = p.b[p.nb++];
+            k.pkts = (const uint8_t *)b.pkts + b.data_off;
+            k.offsets = b.offsets;
+            k.results = verdict_mask ? b.results : nullptr;
+            k.n = b.n;
+            k.stride = b.stride;
+            k.chunk_begin = p.nchunks;
+            p.nchunks += (b.n + COPK_SK_CHUNK - 1) / COPK_SK_CHUNK;
+        }
+        return flush();
+    });
+}
+
+int cop_sketch_query(cop_ctx *c, const cop_sketch *sk, const uint32_t *ips, uint32_t n, uint64_t *out)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_query")) return rc;
+    if (n == 0) return 0;
+    const char *why = "";
+    if (int rc = cop_sketch_query_validate(&sk->cfg, sk->k.ctr, ips, n, out, &why))
+        return set_err(c, rc, "sketch_query: %s", why);
+    return sketch_run(c, "sketch_query", [&](int, hipStream_t s) -> int {
+        const hipError_t e = copk_sketch_query_launch(&sk->k, ips, n, (unsigned long long *)out, s);
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_query launch: %s", hipGetErrorString(e));
+    });
+}
+
+int cop_sketch_decay(cop_ctx *c, cop_sketch *sk, uint32_t shift)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_decay")) return rc;
+    if (shift < 1 || shift > 64) return set_err(c, -EINVAL, "sketch_decay: shift %u not in 1..64", shift);
+    return sketch_run(c, "sketch_decay", [&](int, hipStream_t s) -> int {
+        const hipError_t e = copk_sketch_decay_launch(&sk->k, shift, s);
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_decay launch: %s", hipGetErrorString(e));
+    });
+}
+
+int cop_sketch_police(cop_ctx *c, const cop_sketch *sk, const cop_batch *batches, const cop_police_desc *pol,
+                      uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_police")) return rc;
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "sketch_police: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_sketch_police_validate(&sk->cfg, sk->k.ctr, batches, pol, nb, n_lists, seg, c->cfg.max_batch, &why))
+        return set_err(c, rc, "sketch_police: %s", why);
+    // the lane's scratch: one record per chunk at the worst case the context admits, freed by
+    // cop_destroy alone; launches of one lane run in order, so the next police overwrites it only
+    // after this one's second kernel has read it
+    const uint32_t cpb = (c->cfg.max_batch + COPK_SK_CHUNK - 1) / COPK_SK_CHUNK;
+    const size_t scratch_words = (size_t)c->cfg.max_batches * cpb * n_lists * COPK_SK_SCRATCH_WORDS;
+    return sketch_run(c, "sketch_police", [&](int lane, hipStream_t s) -> int {
+        if (!c->pol_scratch[lane]) HIPCHK(c, hipMalloc(&c->pol_scratch[lane], scratch_words * 4));
+        CopKSkPolice p;
+        memset(&p, 0, sizeof(p));
+        p.sk = sk->k;
+        p.seg = seg ? 1u : 0u;
+        p.scratch = c->pol_scratch[lane];
+        auto flush = [&]() -> int {
+            const hipError_t e = copk_sketch_police_launch(&p, s);
+            p.scratch_begin += p.nchunks;   // <= max_batches * cpb * n_lists: nb <= max_batches, n <= max_batch
+            p.nl = 0;
+            p.nchunks = 0;
+            return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_police launch: %s", hipGetErrorString(e));
+        };
+        for (uint32_t i = 0; i < nb; i++) {
+            const cop_batch &b = batches[i];
+            if (!b.n) continue;
+            const uint32_t chunks = (b.n + COPK_SK_CHUNK - 1) / COPK_SK_CHUNK;
+            for (uint32_t q = 0; q < n_lists; q++) {
+                if (p.nl == COPK_SK_MAXL)
+                    if (int rc = flush()) return rc;
+                CopKSkList &l = p.l[p.nl++];
+                l.pkts = (const uint8_t *)b.pkts + b.data_off;
+                l.offsets = b.offsets;
+                l.idx = b.fwd_idx + (size_t)q * b.n;
+                l.count = b.fwd_count + q;
+                l.out_idx = pol[i].out_idx + (size_t)q * b.n;
+                l.out_count = pol[i].out_count + q;
+                l.status = pol[i].status + 4 * q;
+                l.threshold = pol[i].threshold;
+                l.n = b.n;
+                l.stride = b.stride;
+                l.chunk_begin = p.nchunks;
+                p.nchunks += chunks;
+            }
+        }
+        return flush();
+    });
+}
+
+int cop_sketch_read(cop_ctx *c, const cop_sketch *sk, uint64_t *out, uint64_t cap_words)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_read")) return rc;
+    if (!out) return set_err(c, -EINVAL, "sketch_read: null pointer");
+    if (cap_words < sk->words) return set_err(c, -ENOSPC, "sketch_read: %llu words needed", (unsigned long long)sk->words);
+    if (int rc = sync_lanes(c)) return rc;
+    if (int rc = pmd_pause(c)) return rc;
+    int rc = 0;
+    if (hipMemcpyAsync(out, sk->k.ctr, sk->words * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        rc = set_err(c, -EIO, "sketch_read: copy failed");
+    const int rrc = pmd_resume(c);
+    return rc ? rc : rrc ? rrc : (int)sk->words;
+}
+
+int cop_sketch_device_ptr(cop_ctx *c, const cop_sketch *sk, void **dptr, uint64_t *words)
+{
+    if (!c) return -EINVAL;
+    if (int rc = sketch_of(c, sk, "sketch_device_ptr")) return rc;
+    if (!dptr || !words) return set_err(c, -EINVAL, "sketch_device_ptr: null pointer");
+    *dptr = sk->k.ctr;
+    *words = sk->words;
+    return 0;
 }
 
 /* tests: the patch kernel alone on caller buffers (cop_internal.h) */

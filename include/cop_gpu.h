@@ -656,6 +656,130 @@ int  cop_submit_tx(cop_ctx *ctx, const cop_batch *batches, const cop_tx_desc *tx
 int  cop_tx_gather_host(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t n_lists,
                         int seg, uint32_t max_batch);
 
+/* ------------------------------------------------------------------------ */
+/* Sketch: per-source packet accounting and policing on the device          */
+/* ------------------------------------------------------------------------ */
+
+/* A count-min sketch of the traffic: rows * cols u64 counters in device
+ * memory (row r, column c at word r * cols + c, zero at creation), indexed by
+ * `rows` hashes of a packet's source (or destination) address. The per-rule
+ * counters (COP_CFG_RULE_COUNTERS) say nothing about a source no rule names;
+ * the sketch answers "who is sending all this?" for any address, with an
+ * estimate that is never below the true count.
+ *
+ * Key: k = addr >> (32 - key_depth), addr the packet's source
+ * (COP_SKETCH_KEY_SRC) or destination (_DST) address in host byte order, read
+ * where the pipeline reads it: frame bytes 26..29 / 30..33 of slot and IMIX
+ * batches, record bytes 6..9 / 10..13 of COP_HDR16_STRIDE records (a batch
+ * with stride 16 and no offsets). COP_HDR12_STRIDE records are -EINVAL.
+ *
+ * Hash: z_r = the (r+1)-th output of splitmix64 started at state = seed
+ *   (state += 0x9E3779B97F4A7C15; z = state; z = (z ^ z >> 30) *
+ *   0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^= z >> 31),
+ *   a_r = (uint32_t)z_r | 1, b_r = (uint32_t)(z_r >> 32),
+ *   col_r(k) = (uint32_t)(k * a_r + b_r) >> (32 - log2_cols)   (32-bit arithmetic),
+ *   est(k) = min over r of counter[r][col_r(k)].
+ *
+ * A packet counts iff its EtherType (bytes 12..13) is 0x0800, the high nibble
+ * of byte 14 is 4 (the pipeline's two checks, on the same bytes) and
+ * verdict_mask == 0 or bit results[i].verdict of verdict_mask is set. */
+#define COP_SKETCH_MAX_ROWS 4u
+#define COP_SKETCH_KEY_SRC  0u
+#define COP_SKETCH_KEY_DST  1u
+typedef struct cop_sketch_config {
+    uint32_t rows;       /* 1..COP_SKETCH_MAX_ROWS */
+    uint32_t log2_cols;  /* 4..24: cols = 1 << log2_cols */
+    uint32_t key;        /* COP_SKETCH_KEY_SRC / _DST */
+    uint32_t key_depth;  /* 1..32: the key is addr >> (32 - key_depth); 32 = per host, 24 = per /24 */
+    uint64_t seed;
+} cop_sketch_config;
+typedef struct cop_sketch cop_sketch;   /* owned by one context; several may exist */
+
+/* Police: a batch's forward lists filtered against a threshold into new lists
+ * of the same layout, which cop_tx_gather takes as they are (a cop_batch with
+ * fwd_idx = out_idx, fwd_count = out_count). The lists are the context's,
+ * walked as cop_tx_gather walks them (dense; one per vport with
+ * COP_CFG_DEMUX_PORTS; COP_SEG_PKTS-packet segments with COP_CFG_SEG_LISTS),
+ * with its clamps: a length is clamped to what the layout holds, an index
+ * >= n is read as n - 1. An entry is kept iff its packet does not count as
+ * IPv4 (the two header checks above; verdict_mask plays no part) or
+ * est(key) < threshold. The kept entries are written, as they were read, in
+ * list order: list q's at out_idx + q*n with their number at out_count[q]
+ * and status[4q ..] = {kept, removed, 0, 0}; segment s's at out_idx +
+ * s*COP_SEG_PKTS with their number at out_count[s], and one status for the
+ * batch. Nothing of out_idx is written past a list's (segment's) kept count;
+ * the batch, its lists, its records and the sketch are not written. A batch
+ * with n == 0 is skipped: nothing of it is read or written. */
+typedef struct cop_police_desc {
+    uint64_t  threshold;  /* a list entry is kept iff its packet does not count as IPv4 or est(key) < threshold */
+    uint32_t *out_idx;    /* device; the layout and capacity of the batch's fwd_idx on this context */
+    uint32_t *out_count;  /* device; the layout of fwd_count */
+    uint32_t *status;     /* device, 16-byte aligned; 4 words per forward list: kept, removed, 0, 0 */
+} cop_police_desc;
+
+/* -EINVAL: rows, log2_cols, key or key_depth out of range. The counters are
+ * allocated and zeroed before the call returns. */
+int  cop_sketch_create(cop_ctx *ctx, const cop_sketch_config *cfg, cop_sketch **out);
+/* Waits for the context's queued work, then frees. cop_destroy frees the
+ * sketches that are left. */
+int  cop_sketch_destroy(cop_ctx *ctx, cop_sketch *sk);
+
+/* Every call below but cop_sketch_read is asynchronous, on the next launch
+ * lane, ordered behind everything queued before it on every lane (as
+ * cop_tx_gather is); its outputs are valid after cop_sync. So cop_submit,
+ * cop_sketch_update(1 << COP_FORWARD), cop_sketch_police, cop_tx_gather (of
+ * the police's lists) need no sync between them. While a poll-mode kernel
+ * serves the context every call is synchronous, as cop_lookup_bulk is: the
+ * kernel is paused, the call runs and completes, the kernel is relaunched.
+ * nb == 0 / n == 0 return 0 and launch nothing. -EINVAL (nothing launched,
+ * nothing written): a sketch of another context; nb > max_batches; a batch
+ * with n > max_batch; n > 0 without pkts (police: fwd_idx, fwd_count,
+ * out_idx, out_count, status; query: ips, out); packet starts not 16-byte
+ * aligned (pkts, data_off, a stride that is no multiple of 16: 12-byte
+ * records), a stride of 32; verdict_mask != 0 with results NULL, or with bits
+ * above COP_DROP_NO_PORT; a shift of 0 or above 64. */
+
+/* Adds 1 to the `rows` counters of every counting packet of nb batches. Of a
+ * cop_batch only pkts, offsets, n, stride, data_off and results are read
+ * (results only if verdict_mask != 0). Nothing but the sketch's counters is
+ * written; no pipeline counter is touched. */
+int  cop_sketch_update(cop_ctx *ctx, cop_sketch *sk, const cop_batch *batches, uint32_t nb, uint32_t verdict_mask);
+/* out[i] = est(ips[i] >> (32 - key_depth)): ips n u32 device words in host
+ * byte order (4-byte aligned), out n u64 device words (8-byte aligned, not
+ * overlapping ips or the counters). */
+int  cop_sketch_query(cop_ctx *ctx, const cop_sketch *sk, const uint32_t *ips, uint32_t n, uint64_t *out);
+/* One cop_police_desc per batch (above). Also -EINVAL: a COP_CFG_NO_COMPACT
+ * context; status not 16-byte aligned; an output extent (out_idx, out_count,
+ * status) that overlaps any batch's packets, offsets, records or lists (so
+ * out_idx == fwd_idx) or the sketch's counters. */
+int  cop_sketch_police(cop_ctx *ctx, const cop_sketch *sk, const cop_batch *batches, const cop_police_desc *pol,
+                       uint32_t nb);
+/* Ages the window: every counter >>= shift for shift 1..63; shift 64 zeroes
+ * the counters. */
+int  cop_sketch_decay(cop_ctx *ctx, cop_sketch *sk, uint32_t shift);
+/* Synchronous: waits for the context's queued work and copies the counters to
+ * host memory. Returns the word count (rows * cols), -ENOSPC if cap_words is
+ * smaller, -EINVAL, -EIO. */
+int  cop_sketch_read(cop_ctx *ctx, const cop_sketch *sk, uint64_t *out, uint64_t cap_words);
+/* The counters in device memory, for a caller's own all-reduce (a sketch is
+ * linear: the element-wise sum of two GPUs' sketches is the sketch of their
+ * combined traffic) or a preload with cop_memcpy_h2d. */
+int  cop_sketch_device_ptr(cop_ctx *ctx, const cop_sketch *sk, void **dptr, uint64_t *words);
+
+/* The host mirror (csrc/sketch.c; no GPU needed): the same functions over host
+ * memory, counters a caller's array of rows * cols words. The list layout is
+ * explicit, as cop_tx_gather_host takes it: n_lists lists per batch, seg != 0
+ * for segmented lists (n_lists must be 1), max_batch 0 for no limit on n.
+ * 0 or -EINVAL as above. cop_sketch_params gives a_r and b_r of every row
+ * (COP_SKETCH_MAX_ROWS words each; rows past cfg->rows are 0). */
+int  cop_sketch_params(const cop_sketch_config *cfg, uint32_t a[4], uint32_t b[4]);
+int  cop_sketch_update_host(const cop_sketch_config *cfg, uint64_t *counters, const cop_batch *batches, uint32_t nb,
+                            uint32_t verdict_mask, uint32_t max_batch);
+int  cop_sketch_query_host(const cop_sketch_config *cfg, const uint64_t *counters, const uint32_t *ips, uint32_t n,
+                           uint64_t *out);
+int  cop_sketch_police_host(const cop_sketch_config *cfg, const uint64_t *counters, const cop_batch *batches,
+                            const cop_police_desc *pol, uint32_t nb, uint32_t n_lists, int seg, uint32_t max_batch);
+
 /* End-to-end path from host memory (NIC/KNI mbuf data): gather the first 64
  * bytes of each packet into pinned staging, hipMemcpyAsync H2D, run the
  * pipeline, hipMemcpyAsync D2H of results and forward list. Synchronous. */

@@ -1,0 +1,329 @@
+"""cop_sketch_*_host (csrc/sketch.c), the count-min sketch over host memory
+and the device kernels' mirror, against a numpy restatement of the semantics in
+include/cop_gpu.h (sketch_cases.Spec): the hash, the counting rule, the
+estimate, the police in the three list forms, every -EINVAL. No GPU.
+"""
+import ctypes
+import itertools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+import copgpu as cg
+import sketch_cases as sc
+import tx_cases as tc
+import verdict_patterns as vp
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+EINVAL = -22
+FORMS = {"dense": 1, "seg": 1, "demux": 5}
+
+
+def update_host(spec, cases, mask=0, counters=None, max_batch=0):
+    """cop_sketch_update_host over the cases, checked against the restatement; returns the counters."""
+    got = spec.zeros() if counters is None else counters.copy()
+    want = got.copy()
+    bs, _, keep = sc.host_descs(cases, with_results=True)
+    assert cg.sketch_update_host(spec.cfg(), got, bs, mask, max_batch) == 0
+    for c in cases:
+        c.update(spec, want, mask)
+    assert np.array_equal(got, want), (np.nonzero(got != want), got.sum(), want.sum())
+    return got
+
+
+def assert_overestimates(spec, counters, cases, mask=0):
+    """est(k) >= the true count of k, for every key that was added."""
+    keys = np.concatenate([c.keys(spec)[c.counting(mask)] for c in cases])
+    if len(keys):
+        u, cnt = np.unique(keys, return_counts=True)
+        assert (spec.est(counters, u) >= cnt.astype(np.uint64)).all()
+
+
+@pytest.mark.parametrize("n", sc.NS)
+def test_update_every_layout_and_kind(n):
+    specs = [sc.Spec(r, lc, k, kd, seed=n + 3) for r, lc in ((1, 4), (4, 10), (4, 4), (1, 20))
+             for k, kd in ((0, 32), (1, 24), (0, 8), (1, 1))]
+    for j, (layout, kind) in enumerate(itertools.product(sc.LAYOUTS, sc.KINDS)):
+        spec, mask = specs[(j + n) % len(specs)], sc.VERDICT_MASKS[j % len(sc.VERDICT_MASKS)]
+        case = sc.SkCase(n, kind, layout, seed=j)
+        ctr = update_host(spec, [case], mask)
+        assert_overestimates(spec, ctr, [case], mask)
+        if kind == "mixed" and n >= 255 and mask == 0:
+            assert 0 < case.counting(0).sum() < n
+
+
+@pytest.mark.parametrize("key", [cg.SKETCH_KEY_SRC, cg.SKETCH_KEY_DST])
+@pytest.mark.parametrize("key_depth", [32, 24, 8, 1])
+@pytest.mark.parametrize("log2_cols", [4, 10, 20])
+@pytest.mark.parametrize("rows", [1, 4])
+def test_update_every_config(rows, log2_cols, key_depth, key):
+    spec = sc.Spec(rows, log2_cols, key, key_depth, seed=0xC0FFEE)
+    cases = [sc.SkCase(1027, kind, "s64", seed=3) for kind in ("heavy4", "same24")]
+    ctr = update_host(spec, cases)
+    assert_overestimates(spec, ctr, cases)
+    assert int(ctr.sum()) == rows * 2 * 1027
+    if key_depth == 24 and key == cg.SKETCH_KEY_SRC:        # a /24's hosts share one key
+        k = cases[1].keys(spec)
+        assert len(np.unique(k)) == 1 and len(np.unique(cases[1].src)) == 251
+        assert spec.est(ctr, k[:1])[0] >= 1027
+
+
+@pytest.mark.parametrize("mask", [0, 1, 2, 4, 8, 16, 0x1F, 0x05])
+def test_every_verdict_mask(mask):
+    spec = sc.Spec(4, 10, seed=9)
+    case = sc.SkCase(1027, "mixed", "s128", seed=5)
+    ctr = update_host(spec, [case], mask)
+    assert int(ctr[0].sum()) == int(case.counting(mask).sum())
+    if mask == 0:       # results is not read and may be NULL
+        bs, _, keep = sc.host_descs([case], with_results=False)
+        got = spec.zeros()
+        assert cg.sketch_update_host(spec.cfg(), got, bs, 0, 0) == 0
+        assert np.array_equal(got, ctr)
+
+
+def test_three_layouts_in_one_call_and_a_second_update():
+    spec = sc.Spec(4, 10, seed=11)
+    cases = [sc.SkCase(1027, "heavy4", "s2176", seed=1), sc.SkCase(0, "one", "s64"), sc.SkCase(600, "mixed", "imix", seed=2),
+             sc.SkCase(257, "same24", "rec16", seed=3)]
+    ctr = update_host(spec, cases, 1)
+    ctr = update_host(spec, [sc.SkCase(65, "one", "s64")], 0, counters=ctr)
+    assert_overestimates(spec, ctr, cases, 1)
+
+
+def test_counters_carry_into_the_high_word():
+    spec = sc.Spec(4, 10, seed=13)
+    case = sc.SkCase(8, "one", "s64")
+    pre = spec.zeros()
+    pre[np.arange(4), spec.col(case.keys(spec)[:1])[:, 0].astype(np.int64)] = (1 << 32) - 3
+    ctr = update_host(spec, [case], 0, counters=pre)
+    assert spec.est(ctr, case.keys(spec)[:1])[0] == (1 << 32) + 5
+
+
+@pytest.mark.parametrize("n", [0, 1, 3, 4, 5, 1027])
+def test_query(n):
+    for spec in (sc.Spec(4, 10, 0, 32, seed=1), sc.Spec(1, 4, 1, 24, seed=2), sc.Spec(4, 20, 0, 8, seed=3)):
+        case = sc.SkCase(1027, "heavy4", "s64", seed=4)
+        ctr = update_host(spec, [case])
+        addr = (case.dst if spec.key else case.src)[:n]
+        ips = np.concatenate([addr[: n // 2], addr[: n - n // 2] ^ np.uint64(0x01000001)]).astype(np.uint32)
+        out = np.full(n + 2, sc.U64_MAX - 5, dtype=np.uint64)
+        assert cg.sketch_query_host(spec.cfg(), ctr, ips, out[1:], n) == 0
+        assert np.array_equal(out[1:n + 1], spec.est(ctr, spec.key_of(ips)))
+        assert out[0] == out[n + 1] == sc.U64_MAX - 5
+
+
+def police_host(spec, ctr, cases, max_batch=0):
+    bs, ps, keep = sc.host_descs(cases)
+    before = ctr.copy()
+    rc = cg.sketch_police_host(spec.cfg(), ctr, bs, ps, cases[0].n_lists, cases[0].seg, max_batch)
+    assert np.array_equal(ctr, before)
+    return rc
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+@pytest.mark.parametrize("n", sc.NS)
+def test_police_every_list_form(n, form):
+    K = FORMS[form]
+    spec = sc.Spec(4, 10, n % 2, 32 if n % 3 else 24, seed=n)
+    traffic = sc.SkCase(max(n, 64), "heavy4", "s64", seed=8)
+    ctr = update_host(spec, [traffic, traffic])
+    layouts, kinds = list(sc.LAYOUTS), ("heavy4", "mixed", "same24", "one", "distinct")
+    for j, (name, fwd) in enumerate(tc.masks(n).items()):
+        case = sc.SkCase(n, kinds[j % 5], layouts[j % 5], form, fwd, K, seed=8)
+        med = case.median_threshold(spec, ctr)
+        for th in (0, 1, med, sc.U64_MAX):
+            case.threshold = th
+            case.outs[0] = {k: np.full_like(v, tc.GUARD * 0x01010101) for k, v in case.outs[0].items()}
+            assert police_host(spec, ctr, [case]) == 0
+            e = case.police(spec, ctr)
+            case.check(lambda q, k: case.outs[q][k])
+            st = e["status"][tc.PAD // 4:]
+            if n and th == sc.U64_MAX:        # everything is kept
+                assert sum(int(st[4 * q]) for q in range(case.n_lists)) == int(fwd.sum())
+            if n and th == 0:                 # only what does not count as IPv4 is kept
+                assert sum(int(st[4 * q]) for q in range(case.n_lists)) == int((fwd & ~case.ipv4).sum())
+
+
+@pytest.mark.parametrize("form", ["dense", "seg"])
+def test_police_many_chunks_and_several_batches(form):
+    n = vp.LONG_N
+    spec = sc.Spec(4, 10, seed=21)
+    a = sc.SkCase(n, "heavy4", "s64", form, vp.patterns(n, 256)["alt_tile"], seed=1)
+    b = sc.SkCase(1027, "mixed", "rec16", form, vp.patterns(1027, 256)["bern_63_64"], seed=2)
+    z = sc.SkCase(0, "one", "s64", form)
+    ctr = update_host(spec, [a, b])
+    a.threshold = a.median_threshold(spec, ctr)
+    b.threshold = 3
+    assert police_host(spec, ctr, [a, z, b]) == 0
+    for c in (a, z, b):
+        c.police(spec, ctr)
+        c.check(lambda q, k, c=c: c.outs[q][k])
+    kept = int(a.expect[0]["status"][tc.PAD // 4])
+    assert 0 < kept < int(a.inputs["counts"].sum())
+
+
+@pytest.mark.parametrize("form", list(FORMS))
+def test_police_clamps(form):
+    n, K = 600, FORMS[form]
+    spec = sc.Spec(4, 4, seed=5)
+    case = sc.SkCase(n, "heavy4", "s64", form, vp.patterns(n, 256)["all"], K, seed=6)
+    ctr = update_host(spec, [case])
+    case.inputs["counts"][:] = 0xFFFFFFF0                     # clamped to what the layout holds
+    junk = case.inputs["idx"] == tc.JUNK
+    case.inputs["idx"][junk] = n + 5 + np.arange(junk.sum())  # read as n - 1
+    case.inputs["idx"][::7] += n                              # ... and among the covered entries
+    case.threshold = case.median_threshold(spec, ctr)
+    assert police_host(spec, ctr, [case]) == 0
+    case.police(spec, ctr)
+    case.check(lambda q, k: case.outs[q][k])
+    assert sum(len(e) for _, e in case.lists()) == n * (K if form == "demux" else 1)
+
+
+def test_params_against_hand_computed_values():
+    # splitmix64's published outputs for seeds 0 and 1234567; a = low word | 1, b = high word
+    want = {0: ([0x7B1DCDAF, 0xA1B965F5, 0x8009454F, 0x724C81ED], [0xE220A839, 0x6E789E6A, 0x06C45D18, 0xF88BB8A8]),
+            1234567: ([0xFB08FC85, 0x58540FA5, 0xA3F27C77, 0xE9177B3F], [0x599ED017, 0x2C73F084, 0x883EBCE5, 0x3FBEF740])}
+    for seed, (a, b) in want.items():
+        for rows in (1, 4):
+            ga, gb = cg.sketch_params(cg.sketch_config(rows, 10, 0, 32, seed))
+            assert ga.tolist() == a[:rows] + [0] * (4 - rows) and gb.tolist() == b[:rows] + [0] * (4 - rows)
+            spec = sc.Spec(rows, 10, seed=seed)
+            assert spec.a.tolist() == a[:rows] and spec.b.tolist() == b[:rows]
+    # col_r(k) by hand: k = 1, seed 0, 16 columns: (a0 + b0) mod 2^32 = 0x5D3E75E8 -> top 4 bits = 5
+    assert sc.Spec(1, 4, seed=0).col([1])[0, 0] == 5
+    ctr = np.zeros(16, dtype=np.uint64)
+    ctr[5] = 77
+    out = np.zeros(1, dtype=np.uint64)
+    assert cg.sketch_query_host(cg.sketch_config(1, 4, 0, 32, 0), ctr, np.array([1], dtype=np.uint32), out) == 0
+    assert out[0] == 77
+
+
+def test_einval_leaves_outputs_and_counters_alone():
+    n = 300
+    spec = sc.Spec(4, 10, seed=2)
+    fwd = vp.patterns(n, 256)["alt_wave"]
+
+    def fresh(form="dense", layout="s128"):
+        return sc.SkCase(n, "heavy4", layout, form, fwd, FORMS[form], seed=1, threshold=5)
+
+    def bad_cfg(**kw):
+        f = dict(rows=4, log2_cols=10, key=0, key_depth=32, seed=1)
+        f.update(kw)
+        cfg = cg.sketch_config(**f)
+        assert cg.sketch_params(cfg) is None, kw
+        c = fresh()
+        bs, ps, keep = sc.host_descs([c])
+        ctr = np.full(4 << 10, 7, dtype=np.uint64)
+        out = np.full(4, 9, dtype=np.uint64)
+        assert cg.sketch_update_host(cfg, ctr, bs, 0, 0) == EINVAL
+        assert cg.sketch_police_host(cfg, ctr, bs, ps, 1, False, 0) == EINVAL
+        assert cg.sketch_query_host(cfg, ctr, np.zeros(4, dtype=np.uint32), out) == EINVAL
+        assert (ctr == 7).all() and (out == 9).all()
+
+    for kw in (dict(rows=0), dict(rows=5), dict(log2_cols=3), dict(log2_cols=25), dict(key=2), dict(key_depth=0),
+               dict(key_depth=33)):
+        bad_cfg(**kw)
+
+    def bad(mut, call="both", form="dense", layout="s128", mask=1, **kw):
+        for which in (("update", "police") if call == "both" else (call,)):
+            c = fresh(form, layout)
+            bs, ps, keep = sc.host_descs([c])
+            ctr = np.full((4, 1 << 10), 7, dtype=np.uint64)
+            mut(bs[0], ps[0], ctr)
+            if which == "update":
+                rc = cg.sketch_update_host(spec.cfg(), ctr, bs, kw.get("mask", mask), kw.get("max_batch", 0))
+            else:
+                rc = cg.sketch_police_host(spec.cfg(), ctr, bs, ps, kw.get("n_lists", c.n_lists), c.seg, kw.get("max_batch", 0))
+            assert rc == EINVAL, (mut, which)
+            assert (ctr == 7).all()
+            for k, v in c.outs[0].items():      # untouched: still all guard
+                assert (v.view(np.uint8) == tc.GUARD).all(), k
+
+    def setf(which, field, value):
+        def mut(b, p, ctr):
+            obj = {"b": b, "p": p}[which]
+            setattr(obj, field, value(getattr(obj, field), b, p, ctr) if callable(value) else value)
+        return mut
+
+    bad(setf("b", "pkts", None))
+    bad(setf("b", "pkts", lambda v, b, p, c: v + 8))
+    bad(setf("b", "data_off", 8))
+    bad(setf("b", "stride", 12))                               # COP_HDR12_STRIDE records
+    bad(setf("b", "stride", 120))
+    bad(setf("b", "stride", 32))
+    bad(lambda b, p, c: None, max_batch=n - 1)
+    bad(setf("b", "results", None), call="update")             # verdict_mask != 0 needs the records
+    bad(lambda b, p, c: None, call="update", mask=1 << 5)      # a bit above COP_DROP_NO_PORT
+    for f in ("fwd_idx", "fwd_count"):
+        bad(setf("b", f, None), call="police")
+    for f in ("out_idx", "out_count", "status"):
+        bad(setf("p", f, None), call="police")
+    bad(setf("p", "status", lambda v, b, p, c: v + 4), call="police")
+    bad(setf("p", "out_idx", lambda v, b, p, c: b.fwd_idx), call="police")            # in place
+    bad(setf("p", "out_idx", lambda v, b, p, c: b.fwd_idx + 4 * (n - 1)), call="police")
+    bad(setf("p", "out_idx", lambda v, b, p, c: b.fwd_idx - 4 * (n - 1)), call="police")
+    bad(setf("p", "out_count", lambda v, b, p, c: b.fwd_count), call="police")
+    bad(setf("p", "status", lambda v, b, p, c: b.pkts + 64), call="police")
+    bad(setf("p", "out_count", lambda v, b, p, c: b.results + 8), call="police")
+    bad(setf("p", "status", lambda v, b, p, c: c.ctypes.data + 16), call="police")    # over the counters
+    bad(setf("p", "out_idx", lambda v, b, p, c: b.offsets), call="police", layout="imix")
+    bad(lambda b, p, c: None, call="police", n_lists=9)
+    bad(lambda b, p, c: None, call="police", form="seg", n_lists=2)
+    # query
+    ctr = np.full(4 << 10, 7, dtype=np.uint64)
+    ips, out = np.zeros(8, dtype=np.uint32), np.full(8, 9, dtype=np.uint64)
+    q = lambda i, o, m: cg.lib().cop_sketch_query_host(ctypes.byref(spec.cfg()), ctr.ctypes.data, i, m, o)
+    assert q(None, out.ctypes.data, 8) == EINVAL and q(ips.ctypes.data, None, 8) == EINVAL
+    assert q(ips.ctypes.data, out.ctypes.data + 4, 4) == EINVAL
+    assert q(ips.ctypes.data + 2, out.ctypes.data, 4) == EINVAL
+    assert q(out.ctypes.data + 8, out.ctypes.data, 4) == EINVAL            # out over ips
+    assert q(ips.ctypes.data, ctr.ctypes.data + 64, 4) == EINVAL           # out over the counters
+    assert (ctr == 7).all() and (out == 9).all()
+    # nothing to do: 0, whatever the pointers
+    assert q(None, None, 0) == 0
+    assert cg.sketch_update_host(spec.cfg(), ctr, [], 0, 0) == 0
+    assert cg.sketch_police_host(spec.cfg(), ctr, [], [], 1, False, 0) == 0
+
+
+def test_struct_layouts_match_c(tmp_path):
+    """SketchConfig / PoliceDesc have the C compiler's size and field offsets."""
+    mirrors = {"cop_sketch_config": cg.SketchConfig, "cop_police_desc": cg.PoliceDesc}
+    lines = ['#include <stdio.h>', '#include <stddef.h>', '#include "cop_gpu.h"', "int main(void){"]
+    for cname, py in mirrors.items():
+        lines.append(f'printf("{cname} size %zu\\n", sizeof({cname}));')
+        for f, _ in py._fields_:
+            lines.append(f'printf("{cname} {f} %zu\\n", offsetof({cname}, {f}));')
+    lines.append('printf("consts %u\\n", COP_SKETCH_MAX_ROWS * 100 + COP_SKETCH_KEY_SRC * 10 + COP_SKETCH_KEY_DST);')
+    lines.append("return 0;}")
+    src = tmp_path / "layout.c"
+    src.write_text("\n".join(lines))
+    exe = tmp_path / "layout"
+    r = subprocess.run(["gcc", "-std=c99", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    out = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.split("\n")
+    got = {tuple(l.split()[:-1]): int(l.split()[-1]) for l in out if l.strip()}
+    for cname, py in mirrors.items():
+        assert got[(cname, "size")] == ctypes.sizeof(py), cname
+        for f, _ in py._fields_:
+            assert got[(cname, f)] == getattr(py, f).offset, (cname, f)
+    assert got[("consts",)] == cg.SKETCH_MAX_ROWS * 100 + cg.SKETCH_KEY_SRC * 10 + cg.SKETCH_KEY_DST
+    assert ctypes.sizeof(cg.SketchConfig) == 24 and ctypes.sizeof(cg.PoliceDesc) == 32
+
+
+def test_sketch_under_sanitizers(tmp_path):
+    """tests/c/sketch_check.c, a stand-alone program: sketch.c built with
+    -fsanitize=address,undefined over exactly sized heap blocks, so a byte read
+    or written outside an extent stops it."""
+    exe = tmp_path / "sketch_check"
+    csrc = os.path.join(ROOT, "ghost-dataplane_amd", "csrc")
+    cc = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                         "-I", os.path.join(ROOT, "include"), "-I", csrc,
+                         os.path.join(ROOT, "tests", "c", "sketch_check.c"), os.path.join(csrc, "sketch.c"),
+                         "-o", str(exe)], capture_output=True, text=True)
+    assert cc.returncode == 0, cc.stderr
+    run = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]
+    assert "sketch_check ok" in run.stdout
