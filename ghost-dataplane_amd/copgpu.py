@@ -134,6 +134,19 @@ class PoliceDesc(Structure):
     _fields_ = [("threshold", c_uint64), ("out_idx", c_void_p), ("out_count", c_void_p), ("status", c_void_p)]
 
 
+AEAD_TAG_BYTES = 16    # COP_AEAD_TAG_BYTES
+
+
+class AeadKey(Structure):
+    _fields_ = [("key", ctypes.c_uint8 * 32), ("salt", ctypes.c_uint8 * 4), ("_pad", c_uint32)]
+
+
+class AeadBurst(Structure):
+    _fields_ = [("frames", c_void_p), ("off", c_void_p), ("len", c_void_p), ("count", c_void_p), ("tags", c_void_p),
+                ("ok", c_void_p), ("status", c_void_p), ("cap_bytes", c_uint64), ("seq_base", c_uint64),
+                ("n_frames", c_uint32), ("slot_bytes", c_uint32), ("frame_bytes", c_uint32), ("aad_bytes", c_uint32)]
+
+
 class TraceOpts(Structure):
     _fields_ = [("n_ports", c_uint32), ("pct_non_ipv4", c_uint32), ("pct_bad_version", c_uint32),
                 ("pct_unknown_dst", c_uint32), ("pct_vport_dst", c_uint32),
@@ -199,6 +212,13 @@ SIGNATURES = {
     "cop_sketch_query_host": (c_int, [POINTER(SketchConfig), c_void_p, c_void_p, c_uint32, c_void_p]),
     "cop_sketch_police_host": (c_int, [POINTER(SketchConfig), c_void_p, POINTER(Batch), POINTER(PoliceDesc), c_uint32,
                                        c_uint32, c_int, c_uint32]),
+    "cop_aead_seal": (c_int, [c_void_p, POINTER(AeadKey), POINTER(AeadBurst), c_uint32]),
+    "cop_aead_open": (c_int, [c_void_p, POINTER(AeadKey), POINTER(AeadBurst), c_uint32]),
+    "cop_aead_seal_host": (c_int, [POINTER(AeadKey), POINTER(AeadBurst), c_uint32]),
+    "cop_aead_open_host": (c_int, [POINTER(AeadKey), POINTER(AeadBurst), c_uint32]),
+    "cop_chacha20_block_host": (None, [c_void_p, c_uint32, c_void_p, c_void_p]),
+    "cop_poly1305_host": (None, [c_void_p, c_void_p, c_size_t, c_void_p]),
+    "cop_poly1305_bulk": (c_int, [c_void_p, POINTER(AeadBurst), c_void_p]),
     "cop_rules_load_json": (c_int, [c_char_p, POINTER(c_void_p), POINTER(c_uint32)]),
     "cop_rules_free": (None, [c_void_p]),
     "cop_rules_write_json": (c_int, [c_char_p, c_void_p, c_uint32]),
@@ -974,6 +994,22 @@ class Context:
         """cop_sketch_create: a count-min sketch of rows << log2_cols u64 counters on this context."""
         return Sketch(self, sketch_config(rows, log2_cols, key, key_depth, seed))
 
+    def aead_seal(self, key: "AeadKey", bursts):
+        """cop_aead_seal: ChaCha20-Poly1305 over the frames of the bursts (make_aead_burst) in place,
+        tags written. Asynchronous: valid after sync(); synchronous beside a poll-mode kernel."""
+        arr = (AeadBurst * len(bursts))(*bursts)
+        _check(lib().cop_aead_seal(self.handle, byref(key), arr, len(bursts)), self, "aead_seal")
+
+    def aead_open(self, key: "AeadKey", bursts):
+        """cop_aead_open: tags checked, ok[] written, authentic frames decrypted in place."""
+        arr = (AeadBurst * len(bursts))(*bursts)
+        _check(lib().cop_aead_open(self.handle, byref(key), arr, len(bursts)), self, "aead_open")
+
+    def poly1305_bulk(self, burst: "AeadBurst", otk):
+        """cop_poly1305_bulk: tags[k] = Poly1305(otk[k], frame k); otk a DeviceBuffer or address."""
+        a = otk.addr if isinstance(otk, DeviceBuffer) else otk
+        _check(lib().cop_poly1305_bulk(self.handle, byref(burst), a), self, "poly1305_bulk")
+
     def submit_ring(self, ring: BatchRing, first_slot: int, count: int):
         _check(lib().cop_submit_ring(self.handle, byref(ring), first_slot, count), self, "submit_ring")
 
@@ -1355,3 +1391,56 @@ def tx_gather_host(batches, tx, n_lists: int = 1, seg: bool = False, max_batch: 
     assert len(batches) == len(tx)
     arr, tarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx)
     return lib().cop_tx_gather_host(arr, tarr, len(batches), n_lists, 1 if seg else 0, max_batch)
+
+
+def aead_key(key: bytes, salt: bytes = b"\0\0\0\0") -> AeadKey:
+    """A cop_aead_key: 32 key bytes, 4 salt bytes (nonce bytes 0..3)."""
+    assert len(key) == 32 and len(salt) == 4
+    k = AeadKey()
+    k.key[:] = key
+    k.salt[:] = salt
+    return k
+
+
+def make_aead_burst(frames, tags, status, n_frames: int, cap_bytes: int, off=None, len=None, count=None, ok=None,
+                    seq_base: int = 0, slot_bytes: int = 0, frame_bytes: int = 0, aad_bytes: int = 0) -> AeadBurst:
+    """A cop_aead_burst (DeviceBuffer, address or None each pointer). off / len: both or neither
+    (then the slot form: frame k at k * slot_bytes, frame_bytes long)."""
+    def addr(x):
+        if x is None:
+            return None
+        return x.addr if isinstance(x, DeviceBuffer) else int(x)
+    b = AeadBurst()
+    b.frames, b.off, b.len, b.count = addr(frames), addr(off), addr(len), addr(count)
+    b.tags, b.ok, b.status = addr(tags), addr(ok), addr(status)
+    b.cap_bytes, b.seq_base, b.n_frames = cap_bytes, seq_base & 0xFFFFFFFFFFFFFFFF, n_frames
+    b.slot_bytes, b.frame_bytes, b.aad_bytes = slot_bytes, frame_bytes, aad_bytes
+    b._keep = tuple(x for x in (frames, off, len, count, tags, ok, status) if isinstance(x, DeviceBuffer))
+    return b
+
+
+def aead_seal_host(key: AeadKey, bursts) -> int:
+    """cop_aead_seal_host over host memory (every pointer a host address). Returns the C code."""
+    arr = (AeadBurst * len(bursts))(*bursts)
+    return lib().cop_aead_seal_host(byref(key), arr, len(bursts))
+
+
+def aead_open_host(key: AeadKey, bursts) -> int:
+    arr = (AeadBurst * len(bursts))(*bursts)
+    return lib().cop_aead_open_host(byref(key), arr, len(bursts))
+
+
+def chacha20_block_host(key: bytes, counter: int, nonce: bytes) -> bytes:
+    """cop_chacha20_block_host: one 64-byte ChaCha20 block."""
+    assert len(key) == 32 and len(nonce) == 12
+    out = ctypes.create_string_buffer(64)
+    lib().cop_chacha20_block_host(key, counter, nonce, out)
+    return out.raw
+
+
+def poly1305_host(otk: bytes, msg: bytes) -> bytes:
+    """cop_poly1305_host: the 16-byte tag of msg under the one-time key r || s."""
+    assert len(otk) == 32
+    out = ctypes.create_string_buffer(16)
+    lib().cop_poly1305_host(otk, msg, len(msg), out)
+    return out.raw

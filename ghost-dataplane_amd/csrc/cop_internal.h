@@ -253,6 +253,17 @@ int cop_sketch_police_validate(const cop_sketch_config *cfg, const void *counter
                                const cop_police_desc *pol, uint32_t nb, uint32_t n_lists, int seg,
                                uint32_t max_batch, const char **why);
 
+/* ---- AEAD (aead.c, cop_aead.hip) ------------------------------------------- */
+/* The argument checks cop_aead_seal / _open, cop_poly1305_bulk and the host
+ * mirror share (include/cop_gpu.h "AEAD"): mode one of the three below, otk
+ * cop_poly1305_bulk's keys (NULL otherwise), max_batch 0 for no limit on
+ * n_frames. 0, or -EINVAL / -ENOMEM with *why (may be NULL) the reason. */
+#define COP_AEAD_MODE_SEAL 0
+#define COP_AEAD_MODE_OPEN 1
+#define COP_AEAD_MODE_POLY 2
+int cop_aead_validate(const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb, int mode, const uint8_t *otk,
+                      uint32_t max_batch, const char **why);
+
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,
  * COP_DROPIN_STAGES (process_packet, coprocessor.c:50-65). */

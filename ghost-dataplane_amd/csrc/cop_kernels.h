@@ -327,9 +327,50 @@ struct CopKSkPolice {
     uint32_t seg;
 };
 
+// cop_aead_xor / cop_aead_mac / cop_aead_status (cop_aead.hip): ChaCha20-Poly1305
+// over the frames of tx bursts (cop_aead_seal / _open, cop_poly1305_bulk). One
+// CopKAeBurst per burst, at most COPK_AE_MAXB per launch (the parameters, the
+// key included, are kernel arguments). The MAC kernel runs one frame per lane,
+// COPK_AE_BLOCK frames per workgroup; the keystream kernel `group` lanes per
+// frame (a power of two, 1..32), COPK_AE_BLOCK / group frames per workgroup.
+#define COPK_AE_MAXB 16
+#define COPK_AE_BLOCK 256
+#define COPK_AE_SEAL 0u
+#define COPK_AE_OPEN 1u
+#define COPK_AE_POLY 2u
+struct CopKAeBurst {
+    uint8_t *frames;           // 16-byte aligned
+    const uint32_t *off, *len; // both or neither
+    const uint32_t *count;     // or null
+    uint8_t *tags;             // 16-byte aligned
+    uint32_t *ok;              // open
+    uint32_t *status;          // 16-byte aligned, 4 words
+    const uint8_t *otk;        // COPK_AE_POLY: 32 bytes per frame
+    unsigned long long seq_base;
+    uint32_t cap_bytes;
+    uint32_t n_frames;
+    uint32_t slot_bytes, frame_bytes, aad_bytes;
+    uint32_t group;            // keystream kernel: lanes per frame
+    uint32_t mac_begin;        // first workgroup of this burst in the MAC kernel
+    uint32_t xor_begin;        // and in the keystream kernel
+};
+struct CopKAead {
+    CopKAeBurst b[COPK_AE_MAXB];
+    uint32_t key[8];           // the key's eight little-endian words
+    uint32_t salt;             // nonce word 0
+    uint32_t mode;             // COPK_AE_*
+    uint32_t nb;
+    uint32_t mac_chunks, xor_chunks;   // the two grids
+    uint32_t scratch_begin;    // in MAC workgroups
+    uint32_t *scratch;         // context-owned: COPK_AE_BLOCK / 64 records of 4 words per MAC workgroup, the waves'
+                               // {processed, tag failures, skipped, 0}, from scratch_begin
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+// seal: keystream, MAC, status; open: MAC (writes ok), keystream under ok, status; poly: MAC, status
+hipError_t copk_aead_launch(const CopKAead *p, hipStream_t stream);
 hipError_t copk_sketch_update_launch(const CopKSkUpdate *p, hipStream_t stream);
 hipError_t copk_sketch_police_launch(const CopKSkPolice *p, hipStream_t stream);
 hipError_t copk_sketch_query_launch(const CopKSketch *sk, const uint32_t *ips, uint32_t n, unsigned long long *out,

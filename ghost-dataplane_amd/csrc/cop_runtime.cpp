@@ -391,6 +391,8 @@ struct cop_ctx {
     // lane's first police, at the context's worst case)
     std::vector<cop_sketch *> sketches;
     uint32_t *pol_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    // cop_aead_*: per lane, the MAC waves' status counts (allocated at the lane's first call)
+    uint32_t *aead_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -3994,6 +3996,10 @@ static void sketch_free_all(cop_ctx *c)
         if (p) (void)hipFree(p);
         p = nullptr;
     }
+    for (auto &p : c->aead_scratch) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
 }
 
 static int sketch_of(cop_ctx *c, const cop_sketch *sk, const char *what)
@@ -4233,6 +4239,96 @@ int cop_sketch_device_ptr(cop_ctx *c, const cop_sketch *sk, void **dptr, uint64_
     *dptr = sk->k.ctr;
     *words = sk->words;
     return 0;
+}
+
+// ---- AEAD (cop_aead.hip) ----------------------------------------------------
+// cop_aead_seal / cop_aead_open / cop_poly1305_bulk: every burst with frames
+// becomes one CopKAeBurst; a launch carries up to COPK_AE_MAXB of them with the
+// key, all as kernel arguments, so there is no device object and nothing the
+// host could rewrite under queued work. Ordering is sketch_run's. The lane's
+// scratch holds one 16-byte record per wave of the MAC kernel at the worst case
+// the context admits (max_batches x ceil(max_batch / 256) workgroups), freed by
+// cop_destroy alone: launches of one lane run in order, so the next call's MAC
+// kernel overwrites it only after this call's status kernel has read it.
+static int aead_run(cop_ctx *c, const char *what, uint32_t mode, const cop_aead_key *key, const cop_aead_burst *bursts,
+                    uint32_t nb, const uint8_t *otk)
+{
+    if (!c) return -EINVAL;
+    if (nb == 0) return 0;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "%s: nb %u > max_batches", what, nb);
+    const char *why = "";
+    if (int rc = cop_aead_validate(key, bursts, nb, (int)mode, otk, c->cfg.max_batch, &why))
+        return set_err(c, rc, "%s: %s", what, why);
+    uint32_t live = 0;
+    for (uint32_t i = 0; i < nb; i++) live += bursts[i].n_frames != 0;
+    if (!live) return 0;
+    const size_t scratch_bytes =
+        (size_t)c->cfg.max_batches * ((c->cfg.max_batch + COPK_AE_BLOCK - 1) / COPK_AE_BLOCK) * (COPK_AE_BLOCK / 64) * 16;
+    return sketch_run(c, what, [&](int lane, hipStream_t s) -> int {
+        if (!c->aead_scratch[lane]) HIPCHK(c, hipMalloc(&c->aead_scratch[lane], scratch_bytes));
+        CopKAead p;
+        memset(&p, 0, sizeof(p));
+        p.mode = mode;
+        p.scratch = c->aead_scratch[lane];
+        if (key) {
+            memcpy(p.key, key->key, 32);    // the words are little-endian, as the host is
+            memcpy(&p.salt, key->salt, 4);
+        }
+        auto flush = [&]() -> int {
+            const hipError_t e = copk_aead_launch(&p, s);
+            p.scratch_begin += p.mac_chunks;   // <= max_batches * ceil(max_batch / 256): nb <= max_batches, n_frames <= max_batch
+            p.nb = p.mac_chunks = p.xor_chunks = 0;
+            return e == hipSuccess ? 0 : set_err(c, -EIO, "%s launch: %s", what, hipGetErrorString(e));
+        };
+        for (uint32_t i = 0; i < nb; i++) {
+            const cop_aead_burst &b = bursts[i];
+            if (!b.n_frames) continue;
+            if (p.nb == COPK_AE_MAXB)
+                if (int rc = flush()) return rc;
+            CopKAeBurst &k = p.b[p.nb++];
+            k.frames = (uint8_t *)b.frames;
+            k.off = b.off, k.len = b.len, k.count = b.count;
+            k.tags = b.tags, k.ok = b.ok, k.status = b.status;
+            k.otk = otk;
+            k.seq_base = b.seq_base;
+            k.cap_bytes = (uint32_t)b.cap_bytes;
+            k.n_frames = b.n_frames;
+            k.slot_bytes = b.slot_bytes, k.frame_bytes = b.frame_bytes, k.aad_bytes = b.aad_bytes;
+            // lanes per frame of the keystream kernel: one per 64-byte region that holds text of a
+            // slot frame; off / len bursts, whose lengths only the device knows, 8 lanes that loop
+            k.group = 8;
+            uint32_t regions = 1;
+            if (!b.off) {
+                const uint32_t a = b.aad_bytes < b.frame_bytes ? b.aad_bytes : b.frame_bytes;
+                regions = a < b.frame_bytes ? (b.frame_bytes - (a & ~15u) + 63u) / 64u : 0u;
+                for (k.group = 1; k.group < regions; k.group <<= 1) {}   // regions <= 32
+            }
+            k.mac_begin = p.mac_chunks;
+            k.xor_begin = p.xor_chunks;
+            p.mac_chunks += (b.n_frames + COPK_AE_BLOCK - 1) / COPK_AE_BLOCK;
+            if (mode != COPK_AE_POLY && regions) {
+                const uint32_t per_wg = COPK_AE_BLOCK / k.group;
+                p.xor_chunks += (b.n_frames + per_wg - 1) / per_wg;
+            }
+        }
+        return flush();
+    });
+}
+
+int cop_aead_seal(cop_ctx *c, const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb)
+{
+    return aead_run(c, "aead_seal", COPK_AE_SEAL, key, bursts, nb, nullptr);
+}
+
+int cop_aead_open(cop_ctx *c, const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb)
+{
+    return aead_run(c, "aead_open", COPK_AE_OPEN, key, bursts, nb, nullptr);
+}
+
+int cop_poly1305_bulk(cop_ctx *c, const cop_aead_burst *burst, const uint8_t *otk)
+{
+    if (c && !burst) return set_err(c, -EINVAL, "poly1305_bulk: null burst");
+    return aead_run(c, "poly1305_bulk", COPK_AE_POLY, nullptr, burst, 1, otk);
 }
 
 /* tests: the patch kernel alone on caller buffers (cop_internal.h) */

@@ -780,6 +780,110 @@ int  cop_sketch_query_host(const cop_sketch_config *cfg, const uint64_t *counter
 int  cop_sketch_police_host(const cop_sketch_config *cfg, const uint64_t *counters, const cop_batch *batches,
                             const cop_police_desc *pol, uint32_t nb, uint32_t n_lists, int seg, uint32_t max_batch);
 
+/* ------------------------------------------------------------------------ */
+/* AEAD: ChaCha20-Poly1305 seal / open of tx bursts on the device           */
+/* ------------------------------------------------------------------------ */
+
+/* The frames of a tx burst (what cop_tx_gather leaves: contiguous frames with
+ * their off / len and a status whose word 0 is the frame count) encrypted and
+ * authenticated in place with ChaCha20-Poly1305 (RFC 8439), the AEAD of
+ * WireGuard and of ESP (RFC 7634). One cop_aead_burst per burst.
+ *
+ * Frames: k < min(*count, n_frames), or k < n_frames when count is NULL. No
+ * frame at or past that number is read or written, nor its tag or ok word.
+ *   l   = min(len[k], COP_TX_MAX_FRAME), or frame_bytes in the slot form
+ *         (off and len both NULL);
+ *   ext = (l + 15) & ~15;
+ *   o   = off[k], or k * slot_bytes in the slot form (64-bit arithmetic).
+ * Frame k is skipped when o is not a multiple of 16 or o + ext > cap_bytes: it
+ * is counted in status word 2 and nothing of it is read or written, not its
+ * tag and not its ok word. Otherwise, with a = min(aad_bytes, l):
+ *   bytes [0, a) are the associated data: authenticated and left in clear (the
+ *   Ethernet and IP headers the next hop must read); bytes [a, l) are the
+ *   text. l == a is a valid frame: empty text, authenticated only.
+ *
+ * Nonce of frame k: the 12 bytes salt[0..3] || LE64(seq_base + k), the sum
+ * mod 2^64. Salt zero is WireGuard's nonce, a non-zero salt RFC 7634's.
+ * ChaCha20 block counter 0 gives the Poly1305 one-time key (its first 32
+ * bytes); the text is XORed with the keystream from counter 1 on (at most
+ * counter 32: no counter wraps). The tag is Poly1305 over
+ *   AD || pad16 || ciphertext || pad16 || LE64(a) || LE64(l - a)   (RFC 8439 2.8).
+ *
+ * Seal encrypts [a, l) in place and writes tags[16k .. 16k+16).
+ * Open computes the tag over the ciphertext, compares all 16 bytes with
+ * tags[k], writes ok[k] (1 authentic and decrypted, 0 not), and decrypts in
+ * place only where the tags are equal: a forged frame stays exactly as it was
+ * and is counted in status word 1.
+ * status = {frames processed (not skipped; open: forged ones included), open:
+ * tag failures (seal: 0), frames skipped, 0}.
+ *
+ * What is written: after either call every byte of frames outside some
+ * processed frame's [a, l) holds its previous value (the kernel may
+ * read-modify-write the 16-byte pieces of a frame's own [0, ext) and touches
+ * no byte outside that range); tags / ok are not written at or past the frame
+ * count; off, len and count are only read. A burst with n_frames == 0 is
+ * skipped whole: nothing of it is read or written, its status included.
+ *
+ * Reusing a (key, salt, sequence number) for two different frames is the
+ * caller's misuse: it reveals the XOR of the two texts and lets tags be
+ * forged. Nothing here detects it; the caller advances seq_base by the frame
+ * count (n_frames is enough) from call to call. Frames that overlap inside one
+ * burst (off[] not disjoint) give undefined frame contents. */
+#define COP_AEAD_TAG_BYTES 16u
+typedef struct cop_aead_key {
+    uint8_t  key[32];
+    uint8_t  salt[4];    /* nonce bytes 0..3 */
+    uint32_t _pad;
+} cop_aead_key;
+typedef struct cop_aead_burst {
+    void           *frames;     /* device, 16-byte aligned: a tx burst */
+    const uint32_t *off, *len;  /* device; both or neither. Neither: frame k at k * slot_bytes, length frame_bytes */
+    const uint32_t *count;      /* device or NULL: frames present = min(*count, n_frames): a tx gather's status word 0 */
+    uint8_t        *tags;       /* device, 16-byte aligned, 16 bytes per frame: written by seal, read by open */
+    uint32_t       *ok;         /* open: device, one word per frame (1 authentic and decrypted, 0 not); seal: NULL */
+    uint32_t       *status;     /* device, 16-byte aligned, 4 words: frames processed, open: tag failures,
+                                   frames skipped, 0 */
+    uint64_t        cap_bytes;  /* bytes of frames[]; < 2^32 */
+    uint64_t        seq_base;   /* frame k uses sequence number seq_base + k (mod 2^64) */
+    uint32_t        n_frames, slot_bytes, frame_bytes, aad_bytes;
+} cop_aead_burst;
+
+/* Asynchronous, on the next launch lane, ordered behind everything queued
+ * before it on every lane (as cop_tx_gather is); the outputs are valid after
+ * cop_sync. So cop_submit_tx followed by cop_aead_seal of the gather's burst
+ * (frames, off, len, count = the gather's status) needs no sync in between.
+ * While a poll-mode kernel serves the context the call is synchronous, as
+ * cop_lookup_bulk is: the kernel is paused, the call runs and completes, the
+ * kernel is relaunched. The key travels as kernel arguments: there is no
+ * device object and the caller's key may be reused or wiped on return.
+ * nb == 0 returns 0 and launches nothing. -EINVAL (nothing launched, nothing
+ * written): nb > max_batches; n_frames > max_batch; n_frames > 0 with frames,
+ * tags or status NULL (open: ok); exactly one of off / len; the slot form with
+ * frame_bytes 0 or above COP_TX_MAX_FRAME, or slot_bytes no multiple of 16 or
+ * below frame_bytes; aad_bytes > COP_TX_MAX_FRAME; frames, tags or status not
+ * 16-byte aligned (off, len, count, ok: 4-byte); cap_bytes >= 2^32; ok
+ * non-NULL in seal; any overlap of an extent the call writes (frames[0,
+ * cap_bytes), tags, ok, status) with any other extent of the same or another
+ * burst of the call (frames, off, len, count, tags, ok, status). */
+int  cop_aead_seal(cop_ctx *ctx, const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb);
+int  cop_aead_open(cop_ctx *ctx, const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb);
+/* The host mirror (csrc/aead.c; no GPU needed): the same functions over host
+ * memory, every pointer a host pointer; no limit on nb or n_frames. */
+int  cop_aead_seal_host(const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb);
+int  cop_aead_open_host(const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb);
+/* The building blocks, for the carry edge cases no derived key reaches.
+ * cop_chacha20_block_host: one 64-byte ChaCha20 block (RFC 8439 2.3).
+ * cop_poly1305_host: tag = Poly1305(otk = r || s, msg[0, n)) (RFC 8439 2.5).
+ * cop_poly1305_bulk: the device's Poly1305 alone over one burst, walked as
+ * above: tags[k] = Poly1305(otk[32k .. 32k+32), frame bytes [0, l)), with no
+ * ChaCha and no padding or length blocks; otk is device memory, 32 bytes per
+ * frame, 4-byte aligned; aad_bytes and seq_base are not used, ok is NULL;
+ * status = {frames processed, 0, frames skipped, 0}. Ordering and errors are
+ * cop_aead_seal's (also -EINVAL: otk NULL or overlapped by tags or status). */
+void cop_chacha20_block_host(const uint8_t key[32], uint32_t counter, const uint8_t nonce[12], uint8_t out[64]);
+void cop_poly1305_host(const uint8_t otk[32], const uint8_t *msg, size_t n, uint8_t tag[16]);
+int  cop_poly1305_bulk(cop_ctx *ctx, const cop_aead_burst *burst, const uint8_t *otk);
+
 /* End-to-end path from host memory (NIC/KNI mbuf data): gather the first 64
  * bytes of each packet into pinned staging, hipMemcpyAsync H2D, run the
  * pipeline, hipMemcpyAsync D2H of results and forward list. Synchronous. */
