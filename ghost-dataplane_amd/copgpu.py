@@ -7,6 +7,7 @@ fallback: if libcopgpu.so is missing, importing this module raises.
 from __future__ import annotations
 
 import ctypes
+import errno
 import os
 from ctypes import (POINTER, Structure, byref, c_char_p, c_double, c_int, c_int32,
                     c_size_t, c_uint8, c_uint16, c_uint32, c_uint64, c_void_p)
@@ -863,6 +864,22 @@ class Context:
         f.argtypes = [c_void_p]
         return self.ROUTE_FORMS[_check(f(self.handle), self, "route_form")]
 
+    LAUNCH_FORMS = {0: "off", **ROUTE_FORMS}
+
+    def launch_forms(self):
+        """(firewall form, route form, dynamic LDS bytes) of the context's
+        most recent one-shot launch, as the LDS budget ladder left them
+        (cop_debug_launch_forms); None before any launch."""
+        f = lib().cop_debug_launch_forms
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p]
+        out = np.zeros(3, dtype=np.uint32)
+        rc = f(self.handle, _ptr(out))
+        if rc == -errno.ENOENT:
+            return None
+        _check(rc, self, "launch_forms")
+        return self.LAUNCH_FORMS[int(out[0])], self.LAUNCH_FORMS[int(out[1])], int(out[2])
+
     def lookup_form(self, stage: int) -> str:
         """The table form lookup_bulk uses for a stage now (ROUTE_FORMS names;
         "dir-packed": DIR-24-8 with packed tbl8 groups)."""
@@ -1208,6 +1225,16 @@ class Pmd:
         d["kernel_name"] = (f"cop_pmd<{k & 15}, {(k >> 4) & 15}, {(k >> 8) & 15}, {d['packets_per_tile'] // 256}, "
                             f"{'true' if (k >> 12) & 1 else 'false'}>")
         return d
+
+    def launch_forms(self):
+        """(firewall form, route form, dynamic LDS bytes) of this kernel
+        (cop_debug_pmd_forms; the forms are also in info()["kernel"])."""
+        f = lib().cop_debug_pmd_forms
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p]
+        out = np.zeros(3, dtype=np.uint32)
+        _check(f(self.handle, _ptr(out)), self.ctx, "pmd_forms")
+        return Context.LAUNCH_FORMS[int(out[0])], Context.LAUNCH_FORMS[int(out[1])], int(out[2])
 
     def stop(self):
         if self.handle and self.handle.value:

@@ -217,6 +217,13 @@ int cop_debug_route_form(cop_ctx *c);
  * COP_STAGE_LPM) now; the same COPK_TBL_* values, plus 0x10 when it is
  * DIR-24-8 with packed tbl8 groups. -EINVAL, -ENOENT. */
 int cop_debug_lookup_form(cop_ctx *c, uint32_t stage);
+/* tests: what the context's most recent one-shot launch took after the LDS
+ * budget ladder (cop_submit): out[0] the firewall stage's form, out[1] the
+ * route stage's (COPK_TBL_*, 0 = stage off), out[2] the dynamic LDS bytes per
+ * workgroup. -ENOENT before any launch (a launch refused with -E2BIG is
+ * none). cop_debug_pmd_forms: the same of a poll-mode kernel. */
+int cop_debug_launch_forms(cop_ctx *c, uint32_t out[3]);
+int cop_debug_pmd_forms(const cop_pmd *m, uint32_t out[3]);
 
 /* ---- bulk lookups (lpm_lookup.c) ---------------------------------------- */
 /* What a lookup word keeps of a device entry whose hit bit is set: an NH

@@ -301,6 +301,9 @@ struct cop_ctx {
     uint32_t lds_pad = 0;      // $COP_LDS_PAD: extra LDS bytes per workgroup (occupancy experiments)
     unsigned long long *stamps = nullptr;   // dbg bit 8: per-workgroup phase stamps
     uint32_t inject_submit = 0, inject_wait = 0;   // cop_debug_inject: failures to fake (tests)
+    // cop_debug_launch_forms: what fill_launch chose for the most recent one-shot launch
+    bool last_valid = false;
+    uint32_t last_fw_mode = 0, last_lpm_mode = 0, last_lds_bytes = 0;
     char err[256] = {0};
 
     uint32_t *rt_top = nullptr;
@@ -1082,6 +1085,18 @@ int cop_debug_route_form(cop_ctx *c)
     return pick_mode(c, c->lpm, true, (c->cfg.flags & COP_CFG_LPM_FORCE_DIR24) != 0);
 }
 
+// tests: the table forms (COPK_TBL_*) of the firewall and the route stage and
+// the dynamic LDS bytes of the context's most recent one-shot launch
+int cop_debug_launch_forms(cop_ctx *c, uint32_t out[3])
+{
+    if (!c || !out) return -EINVAL;
+    if (!c->last_valid) return -ENOENT;
+    out[0] = c->last_fw_mode;
+    out[1] = c->last_lpm_mode;
+    out[2] = c->last_lds_bytes;
+    return 0;
+}
+
 static void harvest_one(cop_ctx *c, Lane &L)
 {
     int idx = (L.ev_head - L.ev_count + TIMING_SLOTS) % TIMING_SLOTS;
@@ -1340,6 +1355,10 @@ static int launch_on(cop_ctx *c, Lane &L, CopKParams &p, bool imix, Plan pl, uin
         if (L.ev_count == TIMING_SLOTS) harvest_one(c, L);
         HIPCHK(c, hipEventRecord(L.ev[L.ev_head][0], L.s));
     }
+    c->last_valid = true;
+    c->last_fw_mode = (uint32_t)fw_mode;
+    c->last_lpm_mode = (uint32_t)lpm_mode;
+    c->last_lds_bytes = lds_bytes;
     hipError_t e = copk_launch(&p, fw_mode, lpm_mode, pl.layout, ppt, grid, lds_bytes, L.s);
     if (e != hipSuccess) return set_err(c, -EIO, "launch: %s", hipGetErrorString(e));
     if (p.hit_region && (e = copk_hit_count(&p, grid, COPK_BLOCK * (uint32_t)ppt, L.s)) != hipSuccess)
@@ -3048,6 +3067,16 @@ int cop_pmd_run_timed(cop_pmd *m, uint64_t count, uint64_t *t_post_ns, uint64_t 
     if (t_post_ns) *t_post_ns = t0;
     if (t_done_ns) *t_done_ns = t1;
     return rc;
+}
+
+// tests: the same three words of a poll-mode kernel (cop_debug_launch_forms)
+int cop_debug_pmd_forms(const cop_pmd *m, uint32_t out[3])
+{
+    if (!m || !out) return -EINVAL;
+    out[0] = (uint32_t)m->fw_mode;
+    out[1] = (uint32_t)m->lpm_mode;
+    out[2] = m->lds_bytes;
+    return 0;
 }
 
 int cop_pmd_info(const cop_pmd *m, cop_pmd_info_t *out)

@@ -316,6 +316,14 @@ int  cop_device_pci_bus_id(int device, char *buf, int len);
 /* Upload tables (synchronous). The table may be freed afterwards. */
 int  cop_set_fw_table(cop_ctx *ctx, const cop_lpm_table *t);
 int  cop_set_route_lpm(cop_ctx *ctx, const cop_lpm_table *t);
+/* The vport routing table (65536 entries, port of dst & 0xFFFF; copied). May
+ * be called again at any time after cop_create: the call waits for the
+ * context's launches in flight, which finish with the table they were
+ * submitted under, and every later launch sees the new table (its LDS carve
+ * follows the table's non-uniform 256-entry blocks, see cop_submit). Returns
+ * -EINVAL for a NULL argument and -EBUSY while a poll-mode kernel serves the
+ * context (cop_pmd_stop first; the kernel keeps the table it was started
+ * with). */
 int  cop_set_routing_table(cop_ctx *ctx, const uint16_t *rt /* 65536 */);
 /* setup_rules + lpm_setup in one call: read a rules.json file and build the
  * firewall table with cfg (NULL = reference 1024/24, stop at first error). */
@@ -538,7 +546,17 @@ typedef struct cop_batch {
 /* Enqueue nb batches (nb <= max_batches) as ONE kernel launch on the next
  * launch lane (stream) of the context, round-robin. Launches on different
  * lanes may run concurrently. Asynchronous: returns once queued; outputs are
- * valid after cop_sync. */
+ * valid after cop_sync.
+ * LDS budget: a workgroup holds the routing table's image (1 KiB plus 512
+ * bytes per non-uniform 256-entry block), the stages' interval tables (or the
+ * trie's 16 KiB top level), its scratch words (more with DEMUX_PORTS /
+ * PORT_STATS) and the tile's list stage (1 KiB per 256 packets of the tile),
+ * plus $COP_LDS_PAD. A launch that needs more than 160 KiB looks the route
+ * stage up in its DIR-24-8 image in HBM instead; if that is not enough, the
+ * firewall stage too; if it still does not fit, the call returns -E2BIG
+ * (cop_last_error names LDS) and nothing is launched or written. Results do
+ * not depend on the form taken. cop_submit_ring and cop_pmd_start choose the
+ * same way. */
 int  cop_submit(cop_ctx *ctx, const cop_batch *batches, uint32_t nb);
 /* A ring of equally shaped batch slots resident in device memory (a batch
  * ring buffer in HBM). Slot s: packets at pkts + s*pkts_slot_bytes (packet i
