@@ -148,6 +148,31 @@ class AeadBurst(Structure):
                 ("n_frames", c_uint32), ("slot_bytes", c_uint32), ("frame_bytes", c_uint32), ("aad_bytes", c_uint32)]
 
 
+NEIGH_VALID = 0x1        # COP_NEIGH_VALID
+FWD_OK, FWD_PASS, FWD_SHORT, FWD_BAD_HDR, FWD_OPTIONS, FWD_BAD_CSUM, FWD_TTL, FWD_NO_NEIGH = range(8)   # COP_FWD_*
+FWD_VERIFY_CSUM = 0x1    # cop_fwd_config.flags
+FWD_NO_NH = 0xFFFFFFFF   # COP_FWD_NO_NH
+NEIGH_DT = np.dtype([("dst_mac", "u1", (6,)), ("src_mac", "u1", (6,)), ("port", "<u2"), ("flags", "<u2")])
+
+
+class NeighEntry(Structure):
+    _fields_ = [("dst_mac", ctypes.c_uint8 * 6), ("src_mac", ctypes.c_uint8 * 6), ("port", ctypes.c_uint16),
+                ("flags", ctypes.c_uint16)]
+
+
+class FwdConfig(Structure):
+    _fields_ = [("flags", c_uint32), ("miss_nh", c_uint32)]
+
+
+class FwdCheckDesc(Structure):
+    _fields_ = [("lens", c_void_p), ("out_idx", c_void_p), ("out_count", c_void_p), ("exc_idx", c_void_p),
+                ("exc_count", c_void_p), ("status", c_void_p)]
+
+
+class FwdRwDesc(Structure):
+    _fields_ = [("port", c_void_p * MAX_DEMUX_PORTS), ("status", c_void_p * MAX_DEMUX_PORTS)]
+
+
 class TraceOpts(Structure):
     _fields_ = [("n_ports", c_uint32), ("pct_non_ipv4", c_uint32), ("pct_bad_version", c_uint32),
                 ("pct_unknown_dst", c_uint32), ("pct_vport_dst", c_uint32),
@@ -268,6 +293,18 @@ SIGNATURES = {
     "cop_coll_unique_id": (c_int, [c_void_p]),
     "cop_coll_init": (c_int, [c_void_p, c_void_p, c_int, c_int]),
     "cop_coll_reduce_counters": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int]),
+    "cop_neigh_create": (c_int, [c_void_p, c_uint32, POINTER(c_void_p)]),
+    "cop_neigh_set": (c_int, [c_void_p, c_void_p, c_uint32, c_uint32, c_void_p]),
+    "cop_neigh_destroy": (c_int, [c_void_p, c_void_p]),
+    "cop_neigh_device_ptr": (c_int, [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_uint32)]),
+    "cop_fwd_check": (c_int, [c_void_p, c_void_p, POINTER(FwdConfig), POINTER(Batch), POINTER(FwdCheckDesc), c_uint32]),
+    "cop_fwd_rewrite": (c_int, [c_void_p, c_void_p, POINTER(FwdConfig), POINTER(Batch), POINTER(TxDesc),
+                                POINTER(FwdRwDesc), c_uint32]),
+    "cop_fwd_check_host": (c_int, [c_void_p, c_uint32, POINTER(FwdConfig), POINTER(Batch), POINTER(FwdCheckDesc),
+                                   c_uint32, c_uint32, c_int, c_uint32]),
+    "cop_fwd_rewrite_host": (c_int, [c_void_p, c_uint32, POINTER(FwdConfig), POINTER(Batch), POINTER(TxDesc),
+                                     POINTER(FwdRwDesc), c_uint32, c_uint32, c_int, c_uint32]),
+    "cop_ipv4_csum_host": (ctypes.c_uint16, [c_void_p]),
     "cop_dev_alloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "cop_dev_alloc_ex": (c_int, [c_void_p, c_size_t, c_uint32, POINTER(c_void_p)]),
     "cop_dev_free": (c_int, [c_void_p, c_void_p]),
@@ -1011,6 +1048,25 @@ class Context:
         """cop_sketch_create: a count-min sketch of rows << log2_cols u64 counters on this context."""
         return Sketch(self, sketch_config(rows, log2_cols, key, key_depth, seed))
 
+    def neigh(self, n_entries: int) -> "Neigh":
+        """cop_neigh_create: a neighbour table of n_entries entries on this context, all invalid."""
+        return Neigh(self, n_entries)
+
+    def fwd_check(self, neigh: "Neigh", cfg: "FwdConfig", batches, descs):
+        """cop_fwd_check: the batches' forward lists filtered into the lists of `descs` (one FwdCheckDesc per
+        batch, make_fwd_check). Asynchronous: valid after sync(); synchronous beside a poll-mode kernel."""
+        assert len(batches) == len(descs)
+        arr, darr = (Batch * len(batches))(*batches), (FwdCheckDesc * len(descs))(*descs)
+        _check(lib().cop_fwd_check(self.handle, neigh.handle, byref(cfg), arr, darr, len(batches)), self, "fwd_check")
+
+    def fwd_rewrite(self, neigh: "Neigh", cfg: "FwdConfig", batches, tx, rw):
+        """cop_fwd_rewrite: the frames cop_tx_gather of the same batches and tx left, rewritten in place
+        (one FwdRwDesc per batch, make_fwd_rw)."""
+        assert len(batches) == len(tx) == len(rw)
+        arr, tarr, rarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx), (FwdRwDesc * len(rw))(*rw)
+        _check(lib().cop_fwd_rewrite(self.handle, neigh.handle, byref(cfg), arr, tarr, rarr, len(batches)), self,
+               "fwd_rewrite")
+
     def aead_seal(self, key: "AeadKey", bursts):
         """cop_aead_seal: ChaCha20-Poly1305 over the frames of the bursts (make_aead_burst) in place,
         tags written. Asynchronous: valid after sync(); synchronous beside a poll-mode kernel."""
@@ -1382,6 +1438,85 @@ def sketch_police_host(cfg: SketchConfig, counters: np.ndarray, batches, pol, n_
     arr, parr = (Batch * len(batches))(*batches), (PoliceDesc * len(pol))(*pol)
     return lib().cop_sketch_police_host(byref(cfg), counters.ctypes.data, arr, parr, len(batches), n_lists,
                                         1 if seg else 0, max_batch)
+
+
+def fwd_config(flags: int = 0, miss_nh: int = FWD_NO_NH) -> FwdConfig:
+    cfg = FwdConfig()
+    cfg.flags, cfg.miss_nh = flags, miss_nh
+    return cfg
+
+
+class Neigh:
+    """A context's neighbour table (cop_neigh_*): 16-byte entries (NEIGH_DT) indexed by next hop."""
+
+    def __init__(self, ctx: "Context", n_entries: int):
+        self.ctx, self.handle, self.n_entries = ctx, c_void_p(), n_entries
+        _check(lib().cop_neigh_create(ctx.handle, n_entries, byref(self.handle)), ctx, "neigh_create")
+
+    def set(self, first: int, entries: np.ndarray, count: int | None = None):
+        """cop_neigh_set: entries (NEIGH_DT) to first .. ; synchronous."""
+        a = None if entries is None else np.ascontiguousarray(entries, dtype=NEIGH_DT)
+        n = (0 if a is None else len(a)) if count is None else count
+        _check(lib().cop_neigh_set(self.ctx.handle, self.handle, first, n, None if a is None else a.ctypes.data),
+               self.ctx, "neigh_set")
+
+    def destroy(self):
+        if self.handle:
+            h, self.handle = self.handle, c_void_p()
+            _check(lib().cop_neigh_destroy(self.ctx.handle, h), self.ctx, "neigh_destroy")
+
+    def device_ptr(self):
+        """(device address of the entries, n_entries)."""
+        p, n = c_void_p(), c_uint32()
+        _check(lib().cop_neigh_device_ptr(self.ctx.handle, self.handle, byref(p), byref(n)), self.ctx,
+               "neigh_device_ptr")
+        return p.value, n.value
+
+
+def make_fwd_check(out_idx, out_count, status, lens=None, exc_idx=None, exc_count=None) -> FwdCheckDesc:
+    """A batch's cop_fwd_check_desc (DeviceBuffer, address or None each)."""
+    a = lambda x: x.addr if isinstance(x, DeviceBuffer) else x
+    d = FwdCheckDesc()
+    d.lens, d.out_idx, d.out_count, d.exc_idx, d.exc_count, d.status = (a(x) for x in (lens, out_idx, out_count, exc_idx,
+                                                                                       exc_count, status))
+    d._keep = tuple(x for x in (lens, out_idx, out_count, exc_idx, exc_count, status) if isinstance(x, DeviceBuffer))
+    return d
+
+
+def make_fwd_rw(status, port=None) -> FwdRwDesc:
+    """A batch's cop_fwd_rw_desc: status (and port) one per burst, or a single one."""
+    a = lambda x: x.addr if isinstance(x, DeviceBuffer) else x
+    st = status if isinstance(status, (list, tuple)) else [status]
+    pt = port if isinstance(port, (list, tuple)) else [port] * len(st)
+    d = FwdRwDesc()
+    for q, (s_, p_) in enumerate(zip(st, pt)):
+        d.status[q], d.port[q] = a(s_), a(p_)
+    d._keep = tuple(x for x in list(st) + list(pt) if isinstance(x, DeviceBuffer))
+    return d
+
+
+def fwd_check_host(entries: np.ndarray, cfg: FwdConfig, batches, descs, n_lists: int = 1, seg: bool = False,
+                   max_batch: int = 0, n_entries: int | None = None) -> int:
+    """cop_fwd_check_host over host memory (entries: NEIGH_DT; every pointer a host address). Returns the C code."""
+    assert len(batches) == len(descs)
+    arr, darr = (Batch * len(batches))(*batches), (FwdCheckDesc * len(descs))(*descs)
+    return lib().cop_fwd_check_host(entries.ctypes.data, len(entries) if n_entries is None else n_entries, byref(cfg),
+                                    arr, darr, len(batches), n_lists, 1 if seg else 0, max_batch)
+
+
+def fwd_rewrite_host(entries: np.ndarray, cfg: FwdConfig, batches, tx, rw, n_lists: int = 1, seg: bool = False,
+                     max_batch: int = 0, n_entries: int | None = None) -> int:
+    assert len(batches) == len(tx) == len(rw)
+    arr, tarr, rarr = (Batch * len(batches))(*batches), (TxDesc * len(tx))(*tx), (FwdRwDesc * len(rw))(*rw)
+    return lib().cop_fwd_rewrite_host(entries.ctypes.data, len(entries) if n_entries is None else n_entries,
+                                      byref(cfg), arr, tarr, rarr, len(batches), n_lists, 1 if seg else 0, max_batch)
+
+
+def ipv4_csum_host(hdr) -> int:
+    """cop_ipv4_csum_host: the checksum of a 20-byte IPv4 header (bytes 10..11 taken as zero)."""
+    a = np.ascontiguousarray(hdr, dtype=np.uint8)
+    assert a.size == 20
+    return int(lib().cop_ipv4_csum_host(a.ctypes.data))
 
 
 def make_tx(out, lens=None, copy_bytes: int = 0, slot_bytes: int = 0) -> TxDesc:

@@ -271,6 +271,18 @@ int cop_sketch_police_validate(const cop_sketch_config *cfg, const void *counter
 int cop_aead_validate(const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb, int mode, const uint8_t *otk,
                       uint32_t max_batch, const char **why);
 
+/* ---- L3 forward (fwd.c, cop_fwd.hip) ---------------------------------------- */
+/* The argument checks cop_fwd_check / cop_fwd_rewrite and the host mirror
+ * share (include/cop_gpu.h "L3 forward"): entries the table (device or host,
+ * only its extent is used), max_batch 0 for no limit on n. 0, or -EINVAL /
+ * -ENOMEM with *why (may be NULL) the reason. */
+int cop_fwd_check_validate(const void *entries, uint32_t n_entries, const cop_fwd_config *cfg, const cop_batch *batches,
+                           const cop_fwd_check_desc *desc, uint32_t nb, uint32_t n_lists, int seg, uint32_t max_batch,
+                           const char **why);
+int cop_fwd_rewrite_validate(const void *entries, uint32_t n_entries, const cop_fwd_config *cfg,
+                             const cop_batch *batches, const cop_tx_desc *tx, const cop_fwd_rw_desc *rw, uint32_t nb,
+                             uint32_t n_lists, int seg, uint32_t max_batch, const char **why);
+
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,
  * COP_DROPIN_STAGES (process_packet, coprocessor.c:50-65). */

@@ -366,9 +366,60 @@ struct CopKAead {
                                // {processed, tag failures, skipped, 0}, from scratch_begin
 };
 
+// cop_fwd_mark / cop_fwd_write / cop_fwd_rw / cop_fwd_rw_status (cop_fwd.hip):
+// the L3 forward step (cop_fwd_check, cop_fwd_rewrite). One CopKFwdList per
+// forward list, at most COPK_FWD_MAXL per launch, on the chunk grid of
+// cop_tx.hip: workgroup chunk_begin + c serves chunk c (COPK_FWD_CHUNK list
+// positions) of its list. Scratch per chunk, COPK_FWD_SCRATCH_WORDS words from
+// (scratch_begin + chunk_begin + c): check: words 0..7 the four waves' keep
+// ballots, 8..11 their kept counts, 12 the chunk's entries, 16..19 the waves'
+// COP_FWD_TTL counts, 20..23 their COP_FWD_NO_NEIGH counts, 24..55 the 256
+// 4-bit classes; rewrite: words 0..2 the chunk's {rewritten, PASS, other}.
+#define COPK_FWD_MAXL 16
+#define COPK_FWD_CHUNK 256
+#define COPK_FWD_SCRATCH_WORDS 56
+struct CopKFwdTab {
+    const uint32_t *entries;   // n_entries x 16 bytes: dst_mac, src_mac, port | flags << 16
+    uint32_t n_entries;
+    uint32_t verify;           // COP_FWD_VERIFY_CSUM
+    uint32_t miss_nh;
+    uint32_t _pad;
+};
+struct CopKFwdList {
+    const uint8_t *pkts;       // check: batch pkts + data_off
+    const uint32_t *offsets;   // IMIX batches (check: byte offset of packet i; rewrite: only its being non-null)
+    const uint32_t *lens;      // check, IMIX: frame length of packet i
+    const void *results;       // 8-byte records or null
+    const uint32_t *idx;       // the list's first index word
+    const uint32_t *count;     // its length (dense, per vport), or one word per segment
+    uint32_t *out_idx, *out_count;   // check
+    uint32_t *exc_idx, *exc_count;   // check, or null
+    uint32_t *status;          // 16-byte aligned, 4 words
+    uint8_t *frames;           // rewrite: the burst
+    const uint32_t *off, *len; // rewrite, IMIX
+    const uint32_t *tx_status; // rewrite: the gather's status (word 0: frames written)
+    uint32_t *port;            // rewrite, or null
+    uint32_t n;
+    uint32_t stride;           // check
+    uint32_t slot_bytes;       // rewrite, slot batches
+    uint32_t cap_bytes, cap_frames;   // rewrite
+    uint32_t chunk_begin;      // first workgroup of this list
+};
+struct CopKFwd {
+    CopKFwdTab tab;
+    CopKFwdList l[COPK_FWD_MAXL];
+    uint32_t *scratch;         // context-owned
+    uint32_t scratch_begin;    // in chunks
+    uint32_t nl;
+    uint32_t nchunks;          // the grid
+    uint32_t seg;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+hipError_t copk_fwd_check_launch(const CopKFwd *p, hipStream_t stream);
+hipError_t copk_fwd_rewrite_launch(const CopKFwd *p, hipStream_t stream);
 // seal: keystream, MAC, status; open: MAC (writes ok), keystream under ok, status; poly: MAC, status
 hipError_t copk_aead_launch(const CopKAead *p, hipStream_t stream);
 hipError_t copk_sketch_update_launch(const CopKSkUpdate *p, hipStream_t stream);

@@ -396,6 +396,10 @@ struct cop_ctx {
     uint32_t *pol_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     // cop_aead_*: per lane, the MAC waves' status counts (allocated at the lane's first call)
     uint32_t *aead_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    // cop_neigh_* / cop_fwd_*: the context's neighbour tables, and per lane the check's and the
+    // rewrite's chunk scratch (allocated at the lane's first call, at the context's worst case)
+    std::vector<cop_neigh *> neighs;
+    uint32_t *fwd_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -510,6 +514,7 @@ static void free_retired(cop_ctx *c)
 static void coll_destroy(cop_ctx *c);
 
 static void sketch_free_all(cop_ctx *c);
+static void neigh_free_all(cop_ctx *c);
 
 void cop_destroy(cop_ctx *c)
 {
@@ -585,6 +590,7 @@ void cop_destroy(cop_ctx *c)
     for (auto &e : c->tx_ev)
         if (e) (void)hipEventDestroy(e);
     sketch_free_all(c);
+    neigh_free_all(c);
     free_retired(c);
     if (c->paint_h) (void)hipHostFree(c->paint_h);
     if (c->paint_d) (void)hipFree(c->paint_d);
@@ -4358,6 +4364,224 @@ int cop_poly1305_bulk(cop_ctx *c, const cop_aead_burst *burst, const uint8_t *ot
 {
     if (c && !burst) return set_err(c, -EINVAL, "poly1305_bulk: null burst");
     return aead_run(c, "poly1305_bulk", COPK_AE_POLY, nullptr, burst, 1, otk);
+}
+
+// ---- L3 forward (cop_fwd.hip) -------------------------------------------------
+// A neighbour table is n_entries 16-byte entries of device memory. cop_fwd_check
+// and cop_fwd_rewrite turn every forward list of the batches into one
+// CopKFwdList; a launch carries up to COPK_FWD_MAXL of them with the table's
+// description, all as kernel arguments, so nothing the host could rewrite
+// under queued work. Ordering is sketch_run's. The lane's scratch holds
+// COPK_FWD_SCRATCH_WORDS words per chunk at the worst case the context admits,
+// freed by cop_destroy alone: launches of one lane run in order, so the next
+// call's first kernel overwrites it only after this call's second has read it.
+struct cop_neigh {
+    cop_ctx *owner;
+    uint32_t *entries;
+    uint32_t n_entries;
+};
+
+static void neigh_free_all(cop_ctx *c)
+{
+    for (cop_neigh *g : c->neighs) {
+        if (g->entries) (void)hipFree(g->entries);
+        delete g;
+    }
+    c->neighs.clear();
+    for (auto &p : c->fwd_scratch) {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+}
+
+static int neigh_of(cop_ctx *c, const cop_neigh *g, const char *what)
+{
+    if (!g || std::find(c->neighs.begin(), c->neighs.end(), g) == c->neighs.end())
+        return set_err(c, -EINVAL, "%s: not a neighbour table of this context", what);
+    return 0;
+}
+
+int cop_neigh_create(cop_ctx *c, uint32_t n_entries, cop_neigh **out)
+{
+    if (!c || !out) return -EINVAL;
+    if (n_entries < 1 || n_entries > (1u << 24)) return set_err(c, -EINVAL, "neigh: n_entries must be 1 .. 1 << 24");
+    HIPCHK(c, hipSetDevice(c->device));
+    cop_neigh *g = new cop_neigh();
+    g->owner = c;
+    g->entries = nullptr;
+    g->n_entries = n_entries;
+    const size_t bytes = (size_t)n_entries * 16;
+    // as cop_sketch_create: synchronous, nothing queued work uses, a poll-mode kernel paused
+    if (int rc = pmd_pause(c)) {
+        delete g;
+        return rc;
+    }
+    int rc = 0;
+    if (hipMalloc(&g->entries, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        g->entries = nullptr;
+        rc = set_err(c, -ENOMEM, "neigh: %llu table bytes", (unsigned long long)bytes);
+    } else if (hipMemsetAsync(g->entries, 0, bytes, c->stream) != hipSuccess ||
+               hipStreamSynchronize(c->stream) != hipSuccess) {
+        rc = set_err(c, -EIO, "neigh: zeroing the table");
+    }
+    const int rrc = pmd_resume(c);
+    if (rc || rrc) {
+        if (g->entries) (void)hipFree(g->entries);
+        delete g;
+        return rc ? rc : rrc;
+    }
+    c->neighs.push_back(g);
+    *out = g;
+    return 0;
+}
+
+int cop_neigh_set(cop_ctx *c, cop_neigh *g, uint32_t first, uint32_t count, const cop_neigh_entry *host_entries)
+{
+    if (!c) return -EINVAL;
+    if (int rc = neigh_of(c, g, "neigh_set")) return rc;
+    if (first > g->n_entries || count > g->n_entries - first)
+        return set_err(c, -EINVAL, "neigh_set: entries %u .. +%u leave the table of %u", first, count, g->n_entries);
+    if (count && !host_entries) return set_err(c, -EINVAL, "neigh_set: null entries");
+    if (int rc = sync_lanes(c)) return rc;   // queued work may read the table
+    if (!count) return 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    // a poll-mode kernel is paused for the copy: it holds every workgroup slot it may use, and a copy
+    // the runtime does with a kernel of its own would wait beside it until its idle exit
+    if (int rc = pmd_pause(c)) return rc;
+    int rc = 0;
+    if (hipMemcpyAsync(g->entries + 4 * (size_t)first, host_entries, (size_t)count * 16, hipMemcpyHostToDevice,
+                       c->stream) != hipSuccess ||
+        hipStreamSynchronize(c->stream) != hipSuccess)
+        rc = set_err(c, -EIO, "neigh_set: copy failed");
+    const int rrc = pmd_resume(c);
+    return rc ? rc : rrc;
+}
+
+int cop_neigh_destroy(cop_ctx *c, cop_neigh *g)
+{
+    if (!c) return -EINVAL;
+    if (int rc = neigh_of(c, g, "neigh_destroy")) return rc;
+    if (int rc = sync_lanes(c)) return rc;   // queued work may use the table
+    if (int rc = pmd_pause(c)) return rc;    // hipFree must not wait for a poll-mode kernel
+    (void)hipFree(g->entries);
+    const int rrc = pmd_resume(c);
+    c->neighs.erase(std::find(c->neighs.begin(), c->neighs.end(), g));
+    delete g;
+    return rrc;
+}
+
+int cop_neigh_device_ptr(cop_ctx *c, const cop_neigh *g, void **dptr, uint32_t *n_entries)
+{
+    if (!c) return -EINVAL;
+    if (int rc = neigh_of(c, g, "neigh_device_ptr")) return rc;
+    if (!dptr || !n_entries) return set_err(c, -EINVAL, "neigh_device_ptr: null pointer");
+    *dptr = g->entries;
+    *n_entries = g->n_entries;
+    return 0;
+}
+
+// The lists of the batches, COPK_FWD_MAXL per launch; fill(list, batch index, q) sets what the call adds.
+static int fwd_run(cop_ctx *c, const char *what, const cop_neigh *g, const cop_fwd_config *cfg, const cop_batch *batches,
+                   uint32_t nb, uint32_t n_lists, int seg, bool rewrite,
+                   const std::function<void(CopKFwdList &, uint32_t, uint32_t)> &fill)
+{
+    const uint32_t cpb = (c->cfg.max_batch + COPK_FWD_CHUNK - 1) / COPK_FWD_CHUNK;
+    const size_t scratch_words = (size_t)c->cfg.max_batches * cpb * n_lists * COPK_FWD_SCRATCH_WORDS;
+    return sketch_run(c, what, [&](int lane, hipStream_t s) -> int {
+        if (!c->fwd_scratch[lane]) HIPCHK(c, hipMalloc(&c->fwd_scratch[lane], scratch_words * 4));
+        CopKFwd p;
+        memset(&p, 0, sizeof(p));
+        p.tab.entries = g->entries;
+        p.tab.n_entries = g->n_entries;
+        p.tab.verify = (cfg->flags & COP_FWD_VERIFY_CSUM) ? 1u : 0u;
+        p.tab.miss_nh = cfg->miss_nh;
+        p.seg = seg ? 1u : 0u;
+        p.scratch = c->fwd_scratch[lane];
+        auto flush = [&]() -> int {
+            const hipError_t e = rewrite ? copk_fwd_rewrite_launch(&p, s) : copk_fwd_check_launch(&p, s);
+            p.scratch_begin += p.nchunks;   // <= max_batches * cpb * n_lists: nb <= max_batches, n <= max_batch
+            p.nl = 0;
+            p.nchunks = 0;
+            return e == hipSuccess ? 0 : set_err(c, -EIO, "%s launch: %s", what, hipGetErrorString(e));
+        };
+        for (uint32_t i = 0; i < nb; i++) {
+            const cop_batch &b = batches[i];
+            if (!b.n) continue;
+            const uint32_t chunks = (b.n + COPK_FWD_CHUNK - 1) / COPK_FWD_CHUNK;
+            for (uint32_t q = 0; q < n_lists; q++) {
+                if (p.nl == COPK_FWD_MAXL)
+                    if (int rc = flush()) return rc;
+                CopKFwdList &l = p.l[p.nl++];
+                memset(&l, 0, sizeof(l));
+                l.pkts = (const uint8_t *)b.pkts + b.data_off;
+                l.offsets = b.offsets;
+                l.results = b.results;
+                l.idx = b.fwd_idx + (size_t)q * b.n;
+                l.count = b.fwd_count + q;
+                l.n = b.n;
+                l.stride = b.stride;
+                l.chunk_begin = p.nchunks;
+                fill(l, i, q);
+                p.nchunks += chunks;
+            }
+        }
+        return flush();
+    });
+}
+
+int cop_fwd_check(cop_ctx *c, const cop_neigh *g, const cop_fwd_config *cfg, const cop_batch *batches,
+                  const cop_fwd_check_desc *desc, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (int rc = neigh_of(c, g, "fwd_check")) return rc;
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "fwd_check: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_fwd_check_validate(g->entries, g->n_entries, cfg, batches, desc, nb, n_lists, seg, c->cfg.max_batch,
+                                        &why))
+        return set_err(c, rc, "fwd_check: %s", why);
+    return fwd_run(c, "fwd_check", g, cfg, batches, nb, n_lists, seg, false, [&](CopKFwdList &l, uint32_t i, uint32_t q) {
+        const cop_fwd_check_desc &d = desc[i];
+        const size_t at = (size_t)q * batches[i].n;
+        l.lens = d.lens;
+        l.out_idx = d.out_idx + at;
+        l.out_count = d.out_count + q;
+        l.exc_idx = d.exc_idx ? d.exc_idx + at : nullptr;
+        l.exc_count = d.exc_count ? d.exc_count + q : nullptr;
+        l.status = d.status + 4 * q;
+    });
+}
+
+int cop_fwd_rewrite(cop_ctx *c, const cop_neigh *g, const cop_fwd_config *cfg, const cop_batch *batches,
+                    const cop_tx_desc *tx, const cop_fwd_rw_desc *rw, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (int rc = neigh_of(c, g, "fwd_rewrite")) return rc;
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "fwd_rewrite: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_fwd_rewrite_validate(g->entries, g->n_entries, cfg, batches, tx, rw, nb, n_lists, seg,
+                                          c->cfg.max_batch, &why))
+        return set_err(c, rc, "fwd_rewrite: %s", why);
+    return fwd_run(c, "fwd_rewrite", g, cfg, batches, nb, n_lists, seg, true, [&](CopKFwdList &l, uint32_t i, uint32_t q) {
+        const cop_tx_burst &o = tx[i].out[q];
+        l.frames = (uint8_t *)o.frames;
+        l.off = o.off;
+        l.len = o.len;
+        l.tx_status = o.status;
+        l.port = rw[i].port[q];
+        l.status = rw[i].status[q];
+        l.slot_bytes = tx[i].slot_bytes;
+        l.cap_bytes = (uint32_t)o.cap_bytes;
+        l.cap_frames = o.cap_frames;
+    });
 }
 
 /* tests: the patch kernel alone on caller buffers (cop_internal.h) */

@@ -902,6 +902,168 @@ void cop_chacha20_block_host(const uint8_t key[32], uint32_t counter, const uint
 void cop_poly1305_host(const uint8_t otk[32], const uint8_t *msg, size_t n, uint8_t tag[16]);
 int  cop_poly1305_bulk(cop_ctx *ctx, const cop_aead_burst *burst, const uint8_t *otk);
 
+/* ------------------------------------------------------------------------ */
+/* L3 forward: TTL, checksum and next-hop MAC rewrite of tx bursts          */
+/* ------------------------------------------------------------------------ */
+
+/* What a router does to a frame it forwards, for batches and bursts resident
+ * in device memory: the route stage's next hop (cop_result.route_nh with
+ * COP_FLAG_ROUTE_HIT) indexes a neighbour table that holds the next hop's
+ * MAC addresses; the TTL is decremented, the IPv4 header checksum updated
+ * (RFC 1624 eqn 3) and the two MAC addresses written. cop_fwd_check filters
+ * a batch's forward lists before the gather (what cannot be forwarded goes
+ * to an exception list for the slow path); cop_fwd_rewrite rewrites the
+ * frames of the gathered bursts in place.
+ *
+ * Neighbour table: one per cop_neigh, n_entries 16-byte entries in device
+ * memory indexed by next hop, all zero (invalid) at creation. */
+#define COP_NEIGH_VALID 0x1u
+typedef struct cop_neigh_entry {
+    uint8_t  dst_mac[6];  /* the next hop's address: frame bytes 0..5 */
+    uint8_t  src_mac[6];  /* the egress interface's own: frame bytes 6..11 */
+    uint16_t port;        /* reported in cop_fwd_rw_desc.port[] */
+    uint16_t flags;       /* COP_NEIGH_VALID */
+} cop_neigh_entry;
+typedef struct cop_neigh cop_neigh;   /* owned by one context; several may exist */
+
+/* n_entries 1 .. 1 << 24 (-EINVAL otherwise). The table is allocated and
+ * zeroed before the call returns. */
+int  cop_neigh_create(cop_ctx *ctx, uint32_t n_entries, cop_neigh **out);
+/* Synchronous: waits for the context's queued work, copies host_entries[0,
+ * count) to entries first .. first + count - 1 and returns. -EINVAL: a table
+ * of another context, first + count > n_entries, count > 0 without
+ * host_entries. Allowed while a poll-mode kernel serves the context, as
+ * cop_memcpy_h2d is: that kernel never reads the table (it is paused for the
+ * copy and relaunched, so the copy does not wait for its idle exit). */
+int  cop_neigh_set(cop_ctx *ctx, cop_neigh *ng, uint32_t first, uint32_t count, const cop_neigh_entry *host_entries);
+/* Waits for the context's queued work, then frees. cop_destroy frees the
+ * tables that are left. */
+int  cop_neigh_destroy(cop_ctx *ctx, cop_neigh *ng);
+int  cop_neigh_device_ptr(cop_ctx *ctx, const cop_neigh *ng, void **dptr, uint32_t *n_entries);
+
+/* Classes. A frame (b[0 ..), l bytes long) has the class of the first row
+ * that applies:
+ *   COP_FWD_SHORT     l < 34. Only IMIX frames can be short: l =
+ *                     clamp(lens[i], 1, COP_TX_MAX_FRAME) in the check,
+ *                     min(len[k], COP_TX_MAX_FRAME) in the rewrite (there
+ *                     also a frame whose first 48 bytes do not lie, 16-byte
+ *                     aligned, inside the burst's cap_bytes: no gather leaves
+ *                     one). Nothing of a short frame is read.
+ *   COP_FWD_PASS      b[12..13] != 08 00 or b[14] >> 4 != 4: not IPv4 by the
+ *                     pipeline's two checks; forwarded as it is.
+ *   COP_FWD_BAD_HDR   IHL (b[14] & 15) < 5
+ *   COP_FWD_OPTIONS   IHL > 5: the slow path's. No byte past 33 is ever read.
+ *   COP_FWD_BAD_CSUM  only with COP_FWD_VERIFY_CSUM: with w_j = b[14+2j] << 8
+ *                     | b[15+2j], j = 0..9, fold(sum of w_j) != 0xFFFF; fold
+ *                     adds the carries (v >> 16) back into v & 0xFFFF until
+ *                     v < 0x10000.
+ *   COP_FWD_TTL       b[22] <= 1
+ *   COP_FWD_NO_NEIGH  nh = (results && results[i].flags & COP_FLAG_ROUTE_HIT)
+ *                     ? results[i].route_nh & 0xFFFFFF : cfg.miss_nh;
+ *                     nh >= n_entries or entry nh lacks COP_NEIGH_VALID.
+ *                     miss_nh = COP_FWD_NO_NH puts every route miss here.
+ *   COP_FWD_OK        otherwise */
+#define COP_FWD_OK        0u
+#define COP_FWD_PASS      1u
+#define COP_FWD_SHORT     2u
+#define COP_FWD_BAD_HDR   3u
+#define COP_FWD_OPTIONS   4u
+#define COP_FWD_BAD_CSUM  5u
+#define COP_FWD_TTL       6u
+#define COP_FWD_NO_NEIGH  7u
+#define COP_FWD_VERIFY_CSUM 0x1u
+#define COP_FWD_NO_NH     0xFFFFFFFFu
+typedef struct cop_fwd_config {
+    uint32_t flags;    /* COP_FWD_VERIFY_CSUM */
+    uint32_t miss_nh;  /* the next hop of a packet without a route hit */
+} cop_fwd_config;
+
+/* Check: a batch's forward lists filtered into new lists of the same layout,
+ * which cop_tx_gather takes as they are (cop_sketch_police's shape). The
+ * lists are the context's, walked as cop_tx_gather walks them, with its
+ * clamps: a length is clamped to what the layout holds, an entry e >= n is
+ * read as packet i = n - 1. The class of an entry is that of packet i's
+ * frame (where cop_batch puts it; of the batch's records only results[i] is
+ * read, and only when results is not NULL). An entry is kept iff its class
+ * is COP_FWD_OK or COP_FWD_PASS. The kept entries are written, as they were
+ * read, in list order: list q's at out_idx + q*n with their number at
+ * out_count[q]; segment s's at out_idx + s*COP_SEG_PKTS with their number at
+ * out_count[s]. The removed entries go the same way to exc_idx / exc_count
+ * (when given), each as min(e, n - 1) | class << 28. status[4q ..] = {kept,
+ * removed, removed as COP_FWD_TTL, removed as COP_FWD_NO_NEIGH}; segmented
+ * lists have one status per batch. Nothing of out_idx / exc_idx is written
+ * past a list's (segment's) kept / removed count; the batch, its lists, its
+ * records and the table are not written. A batch with n == 0 is skipped:
+ * nothing of it is read or written. */
+typedef struct cop_fwd_check_desc {
+    const uint32_t *lens;   /* IMIX batches: device, n words (as cop_tx_desc.lens); slot batches: NULL */
+    uint32_t *out_idx;      /* device; the layout and capacity of the batch's fwd_idx on this context */
+    uint32_t *out_count;    /* device; the layout of fwd_count */
+    uint32_t *exc_idx;      /* device or NULL (then exc_count too): the removed entries, out_idx's layout */
+    uint32_t *exc_count;
+    uint32_t *status;       /* device, 16-byte aligned; 4 words per forward list */
+} cop_fwd_check_desc;
+
+/* Rewrite: after cop_tx_gather of the same batches and tx. For burst q of a
+ * batch (one per forward list; one per batch for segmented lists):
+ *   W = min(tx.out[q].status[0], cap_frames, the list's clamped length);
+ *   frame k < W is the frame of list position k (segmented lists: of the
+ *   concatenation of the segments), its packet i = min(entry, n - 1), its
+ *   bytes at frames + k * slot_bytes, or at frames + off[k] for IMIX.
+ * The class comes from the frame's own bytes in the burst, results[i] and the
+ * table. A COP_FWD_OK frame is rewritten: b[0..5] = dst_mac, b[6..11] =
+ * src_mac, b[22] -= 1 and, in big-endian 16-bit words with m = b[22] << 8 |
+ * b[23] (before the decrement), m' = m - 0x0100, HC = b[24] << 8 | b[25]:
+ *   HC' = ~fold(~HC + ~m + m') & 0xFFFF          (RFC 1624 eqn 3)
+ * into b[24..25], whether or not HC was valid. No other frame is written.
+ * port[q] (when not NULL): word k < W = the entry's port for an OK frame,
+ * else 0xFFFF. status[q] = {rewritten, untouched COP_FWD_PASS, untouched
+ * other class, 0}. No byte of frames outside bytes [0, 26) of an OK frame
+ * changes (the kernel may read-modify-write the frame's own 16-byte pieces in
+ * [0, 32)); no frame at or past W is read or written, nor its port word; the
+ * gather's off, len and status are only read. A batch with n == 0 is skipped.
+ * Calling it twice decrements twice. */
+typedef struct cop_fwd_rw_desc {
+    uint32_t *port[COP_MAX_DEMUX_PORTS];     /* device or NULL: cap_frames words */
+    uint32_t *status[COP_MAX_DEMUX_PORTS];   /* device, 16-byte aligned, 4 words */
+} cop_fwd_rw_desc;
+
+/* Both calls are asynchronous, on the next launch lane, ordered behind
+ * everything queued before them on every lane (as cop_tx_gather and
+ * cop_sketch_police are); the outputs are valid after cop_sync. So
+ * cop_submit, cop_fwd_check, cop_tx_gather (of the check's lists),
+ * cop_fwd_rewrite and cop_aead_seal need no sync between them. While a
+ * poll-mode kernel serves the context the calls are synchronous, as
+ * cop_lookup_bulk is. nb == 0 returns 0 and launches nothing.
+ * -EINVAL (nothing launched, nothing written): a table of another context;
+ * nb > max_batches; n > max_batch or n > 1 << 28; n > 0 with pkts, fwd_idx,
+ * fwd_count, out_idx, out_count or status NULL (rewrite: a status NULL); a
+ * COP_CFG_NO_COMPACT context; packet starts not 16-byte aligned (pkts,
+ * data_off, stride); a slot batch's stride below 48 (16- and 32-byte
+ * records); an IMIX batch without lens, or lens on a slot batch; results not
+ * 8-byte aligned; status not 16-byte aligned; exactly one of exc_idx /
+ * exc_count; unknown cfg.flags; in the rewrite copy_bytes < 48, an IMIX burst
+ * without off and len, and every argument error of cop_tx_gather; any overlap
+ * of an extent the call writes (check: out_idx, out_count, exc_idx,
+ * exc_count, status; rewrite: frames[0, cap_bytes), port, status) with any
+ * other extent of the call or with the table. */
+int  cop_fwd_check(cop_ctx *ctx, const cop_neigh *ng, const cop_fwd_config *cfg, const cop_batch *batches,
+                   const cop_fwd_check_desc *desc, uint32_t nb);
+int  cop_fwd_rewrite(cop_ctx *ctx, const cop_neigh *ng, const cop_fwd_config *cfg, const cop_batch *batches,
+                     const cop_tx_desc *tx, const cop_fwd_rw_desc *rw, uint32_t nb);
+/* The host mirror (csrc/fwd.c; no GPU needed): the same functions over host
+ * memory, entries a caller's array of n_entries entries; the list layout
+ * explicit as cop_tx_gather_host takes it; max_batch 0 for no limit on n.
+ * cop_ipv4_csum_host: the full recompute over a 20-byte header, bytes 10..11
+ * taken as zero; returns the value whose high byte goes to byte 10. */
+int  cop_fwd_check_host(const cop_neigh_entry *entries, uint32_t n_entries, const cop_fwd_config *cfg,
+                        const cop_batch *batches, const cop_fwd_check_desc *desc, uint32_t nb, uint32_t n_lists,
+                        int seg, uint32_t max_batch);
+int  cop_fwd_rewrite_host(const cop_neigh_entry *entries, uint32_t n_entries, const cop_fwd_config *cfg,
+                          const cop_batch *batches, const cop_tx_desc *tx, const cop_fwd_rw_desc *rw, uint32_t nb,
+                          uint32_t n_lists, int seg, uint32_t max_batch);
+uint16_t cop_ipv4_csum_host(const uint8_t hdr[20]);
+
 /* End-to-end path from host memory (NIC/KNI mbuf data): gather the first 64
  * bytes of each packet into pinned staging, hipMemcpyAsync H2D, run the
  * pipeline, hipMemcpyAsync D2H of results and forward list. Synchronous. */
