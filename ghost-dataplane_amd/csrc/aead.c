@@ -165,22 +165,6 @@ void cop_poly1305_host(const uint8_t otk[32], const uint8_t *msg, size_t n, uint
 }
 
 /* ---- argument checks ----------------------------------------------------------- */
-typedef struct {
-    uintptr_t a, b; /* [a, b) */
-    int written;
-} span;
-
-static span mk(const void *p, uint64_t bytes, int written)
-{
-    span s = {(uintptr_t)p, (uintptr_t)p + (p ? bytes : 0), written};
-    return s;
-}
-
-static int meets(span x, span y)
-{
-    return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b;
-}
-
 int cop_aead_validate(const cop_aead_key *key, const cop_aead_burst *bursts, uint32_t nb, int mode, const uint8_t *otk,
                       uint32_t max_batch, const char **why)
 {
@@ -223,7 +207,7 @@ int cop_aead_validate(const cop_aead_key *key, const cop_aead_burst *bursts, uin
         return 0;
     }
     /* nothing the call writes (frames, tags, ok, status) over any other extent of any burst */
-    span *e = (span *)malloc((size_t)live * 8 * sizeof(span));
+    cop_extent *e = (cop_extent *)malloc((size_t)live * 8 * sizeof(cop_extent));
     *why = "out of memory";
     if (!e) return -ENOMEM;
     uint32_t ne = 0;
@@ -231,21 +215,16 @@ int cop_aead_validate(const cop_aead_key *key, const cop_aead_burst *bursts, uin
         const cop_aead_burst *b = &bursts[i];
         const uint64_t n = b->n_frames;
         if (!n) continue;
-        e[ne++] = mk(b->frames, b->cap_bytes, 1);
-        e[ne++] = mk(b->tags, 16 * n, 1);
-        e[ne++] = mk(b->ok, 4 * n, 1);
-        e[ne++] = mk(b->status, 16, 1);
-        e[ne++] = mk(b->off, 4 * n, 0);
-        e[ne++] = mk(b->len, 4 * n, 0);
-        e[ne++] = mk(b->count, 4, 0);
-        if (mode == COP_AEAD_MODE_POLY) e[ne++] = mk(otk, 32 * n, 0);
+        cop_extent_put(e, &ne, b->frames, b->cap_bytes, 1);
+        cop_extent_put(e, &ne, b->tags, 16 * n, 1);
+        cop_extent_put(e, &ne, b->ok, 4 * n, 1);
+        cop_extent_put(e, &ne, b->status, 16, 1);
+        cop_extent_put(e, &ne, b->off, 4 * n, 0);
+        cop_extent_put(e, &ne, b->len, 4 * n, 0);
+        cop_extent_put(e, &ne, b->count, 4, 0);
+        if (mode == COP_AEAD_MODE_POLY) cop_extent_put(e, &ne, otk, 32 * n, 0);
     }
-    int rc = 0;
-    for (uint32_t x = 0; x < ne && !rc; x++) {
-        if (!e[x].written) continue;
-        for (uint32_t y = 0; y < ne && !rc; y++)
-            if (y != x && meets(e[x], e[y])) rc = -EINVAL;
-    }
+    const int rc = cop_extents_clash(e, ne, 0) ? -EINVAL : 0;
     free(e);
     *why = rc ? "frames, tags, ok or status overlaps another extent of the call" : "";
     return rc;

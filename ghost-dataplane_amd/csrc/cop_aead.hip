@@ -40,26 +40,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cop_kernels.h"
+#include "cop_chunk.h"   // item_of, wave_sum
 
 namespace {
 
 constexpr int BLOCK = COPK_AE_BLOCK;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t burst_of_mac(const CopKAead &p, uint32_t wg)
-{
-    uint32_t bi = 0;
-    while (bi + 1 < p.nb && wg >= p.b[bi + 1].mac_begin) bi++;
-    return bi;
-}
-
-__device__ __forceinline__ uint32_t burst_of_xor(const CopKAead &p, uint32_t wg)
-{
-    uint32_t bi = 0;
-    while (bi + 1 < p.nb && wg >= p.b[bi + 1].xor_begin) bi++;
-    return bi;
-}
 
 __device__ __forceinline__ uint32_t frames_present(const CopKAeBurst &B)
 {
@@ -144,7 +129,7 @@ __device__ __forceinline__ void xor_region(const uint32_t (&prev)[4], const uint
 
 __global__ __launch_bounds__(BLOCK) void cop_aead_xor(const CopKAead p)
 {
-    const CopKAeBurst &B = p.b[burst_of_xor(p, blockIdx.x)];
+    const CopKAeBurst &B = p.b[item_of(p.nb, blockIdx.x, [&](uint32_t i) { return p.b[i].xor_begin; })];
     const uint32_t G = B.group, tid = threadIdx.x;
     const uint32_t j = tid & (G - 1u), g = tid / G;
     const uint32_t k = (blockIdx.x - B.xor_begin) * (BLOCK / G) + g;
@@ -307,7 +292,7 @@ __device__ __forceinline__ void poly_span(Poly &P, const uint8_t *f, uint32_t ex
 
 __global__ __launch_bounds__(BLOCK) void cop_aead_mac(const CopKAead p)
 {
-    const CopKAeBurst &B = p.b[burst_of_mac(p, blockIdx.x)];
+    const CopKAeBurst &B = p.b[item_of(p.nb, blockIdx.x, [&](uint32_t i) { return p.b[i].mac_begin; })];
     const uint32_t k = (blockIdx.x - B.mac_begin) * BLOCK + threadIdx.x;
     const bool present = k < frames_present(B);
     uint32_t o = 0, l = 0;
@@ -358,13 +343,6 @@ __global__ __launch_bounds__(BLOCK) void cop_aead_mac(const CopKAead p)
     if ((threadIdx.x & 63u) == 0u)
         ((u32x4 *)p.scratch)[(size_t)(p.scratch_begin + blockIdx.x) * (BLOCK / 64) + (threadIdx.x >> 6)] =
             u32x4{n_live, n_bad, n_present - n_live, 0u};
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
 }
 
 // one workgroup per burst: the sum of the records its MAC workgroups left

@@ -2,23 +2,19 @@
 // the L3 forward step on forward lists and tx bursts (cop_fwd_check,
 // cop_fwd_rewrite, include/cop_gpu.h "L3 forward"; host mirror: fwd.c).
 //
-// Both calls run on the chunk grid of cop_tx.hip: one workgroup per 256
-// consecutive positions of one list (a segment of a segmented list), the grid
-// sized from n, no atomics and no workgroup waiting for another.
+// Both calls run on the chunk grid of cop_chunk.h.
 //
 // Check: cop_fwd_mark loads pieces 0..2 (bytes 0..47) of every entry's packet
 // as the pipeline's loaders do, gathers results[i] (8 bytes) and the
-// neighbour entry (one 16-byte load), and writes the chunk's keep ballots, its
-// waves' kept / TTL / NO_NEIGH counts and the 4-bit classes to context-owned
-// scratch. cop_fwd_write, on the same grid, places the kept and the removed
-// entries: a chunk's bases are the sums of the earlier chunks' counts (dense,
-// per vport) or the segment's own start, a lane's place the bits below it.
-// Chunk 0 of a list, which exists for every list, sums all chunks and writes
-// status (and a dense list's counts); a segment's chunk writes its own count
-// words. The classes are computed once, in the first kernel.
+// neighbour entry (one 16-byte load), and adds to the chunk's mark record its
+// waves' TTL / NO_NEIGH counts and the 4-bit classes. cop_fwd_write, on the
+// same grid, places the kept and the removed entries (a removed entry's place:
+// the entries before it less the kept ones). Chunk 0 of a list writes status
+// (and a dense list's counts); a segment's chunk writes its own count words.
+// The classes are computed once, in the first kernel.
 //
 // Rewrite: cop_fwd_rw, one frame per lane. A chunk's first frame k0 is 256c
-// or the sum of the earlier segments' counts (cop_tx_copy's reduction). A lane
+// or the sum of the earlier segments' counts (chunk_locate). A lane
 // loads pieces 0 and 1 of its frame in the burst (piece 2 only to verify the
 // checksum), classifies, and stores the two pieces of an OK frame: piece 0 is
 // the entry's first three words and the frame's own fourth, piece 1 the
@@ -28,23 +24,20 @@
 //
 // Only vector loads and stores, in plain C++.
 //
-// Bounds: a list index >= n is read as n - 1; a count is clamped to what the
-// layout holds, so a kept or removed entry's place is below the list's
-// (segment's) capacity; nh is compared with n_entries before the entry is
-// loaded; W <= cap_frames, and a frame is touched only if its first 48 bytes
-// lie, 16-byte aligned, inside cap_bytes (64-bit arithmetic); an IMIX packet
-// of the check is read only if its clamped length is >= 34, which the caller
-// backs with 48 readable bytes.
+// Bounds: the lists' are cop_chunk.h's; nh is compared with n_entries before
+// the entry is loaded; W <= cap_frames, and a frame is touched only if its
+// first 48 bytes lie, 16-byte aligned, inside cap_bytes (64-bit arithmetic);
+// an IMIX packet of the check is read only if its clamped length is >= 34,
+// which the caller backs with 48 readable bytes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cop_kernels.h"
+#include "cop_chunk.h"
 
 namespace {
 
-constexpr int BLOCK = COPK_FWD_CHUNK;
+constexpr int BLOCK = CHUNK;
 constexpr uint32_t SW = COPK_FWD_SCRATCH_WORDS;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 
 enum : uint32_t { OK = 0, PASS = 1, SHORT = 2, BAD_HDR = 3, OPTIONS = 4, BAD_CSUM = 5, TTL = 6, NO_NEIGH = 7 };
@@ -82,65 +75,22 @@ __device__ __forceinline__ uint32_t class_of(const CopKFwdTab &t, const u32x4 &p
     return ((ent.w >> 16) & 1u) ? OK : NO_NEIGH;
 }
 
-__device__ __forceinline__ uint32_t list_of(const CopKFwd &p, uint32_t wg)
-{
-    uint32_t li = 0;
-    while (li + 1 < p.nl && wg >= p.l[li + 1].chunk_begin) li++;
-    return li;
-}
-
-__device__ __forceinline__ uint32_t chunk_cap(uint32_t n, uint32_t c)
-{
-    const uint32_t first = c * BLOCK;
-    return n > first ? min(n - first, (uint32_t)BLOCK) : 0u;
-}
-
-// entries of chunk c of a list over a batch of n packets
-__device__ __forceinline__ uint32_t chunk_count(const CopKFwdList &L, uint32_t seg, uint32_t c)
-{
-    if (seg) return min(L.count[c], chunk_cap(L.n, c));
-    const uint32_t total = min(L.count[0], L.n), first = c * BLOCK;
-    return total > first ? min(total - first, (uint32_t)BLOCK) : 0u;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// sums of four values over the workgroup (every thread gets them)
-__device__ __forceinline__ void block_sum4(uint32_t (&v)[4], uint32_t (*red)[4], int lane, int wave)
-{
-#pragma unroll
-    for (int j = 0; j < 4; j++) v[j] = wave_sum(v[j]);
-    __syncthreads();   // red may still be read from an earlier use
-    if (lane == 0)
-#pragma unroll
-        for (int j = 0; j < 4; j++) red[wave][j] = v[j];
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < 4; j++) v[j] = red[0][j] + red[1][j] + red[2][j] + red[3][j];
-}
-
 __global__ __launch_bounds__(BLOCK) void cop_fwd_mark(const CopKFwd p)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKFwdList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t cnt = chunk_count(L, p.seg, c);
+    const CopKFwdList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    const uint32_t cnt = chunk_count(L.h, p.seg, c);
     uint32_t cls = 0xFu;   // no entry
     if ((uint32_t)tid < cnt) {
-        const uint32_t i = min(L.idx[(size_t)c * BLOCK + tid], L.n - 1u);
+        const uint32_t i = chunk_entry(L.h, c, tid);
         bool is_short = false;
         const uint8_t *f;
-        if (L.offsets) {
+        if (L.h.offsets) {
             is_short = min(max(L.lens[i], 1u), COPK_TX_MAX_FRAME) < 34u;
-            f = L.pkts + (unsigned long long)L.offsets[i];
+            f = L.h.pkts + (unsigned long long)L.h.offsets[i];
         } else {
-            f = L.pkts + (unsigned long long)i * L.stride;
+            f = L.h.pkts + (unsigned long long)i * L.h.stride;
         }
         cls = SHORT;
         if (!is_short) {
@@ -149,7 +99,6 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_mark(const CopKFwd p)
             cls = class_of(p.tab, p0, p1, p2.x, L.results, i, ent);
         }
     }
-    const unsigned long long bits = __ballot(cls <= PASS);
     const unsigned long long ttl = __ballot(cls == TTL), nn = __ballot(cls == NO_NEIGH);
     // eight lanes' classes in one word
     uint32_t packed = cls << (4 * (lane & 7));
@@ -159,50 +108,32 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_mark(const CopKFwd p)
     uint32_t *const sc = p.scratch + (size_t)(p.scratch_begin + blockIdx.x) * SW;
     if ((lane & 7) == 0) sc[24 + (tid >> 3)] = packed;
     if (lane == 0) {
-        sc[2 * wave] = (uint32_t)bits;
-        sc[2 * wave + 1] = (uint32_t)(bits >> 32);
-        sc[8 + wave] = (uint32_t)__popcll(bits);
         sc[16 + wave] = (uint32_t)__popcll(ttl);
         sc[20 + wave] = (uint32_t)__popcll(nn);
     }
-    if (tid == 0) sc[12] = cnt;
+    mark_put(sc, cls <= PASS, cnt);
 }
 
 __global__ __launch_bounds__(BLOCK) void cop_fwd_write(const CopKFwd p)
 {
     __shared__ uint32_t red[4][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKFwdList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t nchunk = (L.n + BLOCK - 1) / BLOCK;
-    const uint32_t *const sc0 = p.scratch + (size_t)(p.scratch_begin + L.chunk_begin) * SW;
-    const uint32_t *const sc = sc0 + (size_t)c * SW;
-    const uint32_t cnt = sc[12];
-    if (!cnt && c != 0) {   // past the list's end, or an empty segment
+    const uint32_t tid = threadIdx.x;
+    const CopKFwdList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    const uint32_t *const sc0 = p.scratch + (size_t)(p.scratch_begin + L.h.chunk_begin) * SW;
+    MarkAt m;
+    uint32_t v[4] = {0u, 0u, 0u, 0u};   // {kept, entries, TTL, NO_NEIGH} of the chunks before this one; chunk 0: of every chunk
+    if (!mark_get(sc0, SW, p.seg, c, (L.h.n + BLOCK - 1) / BLOCK, m, v, red, [](const uint32_t *x, uint32_t (&v)[4]) {
+            const u32x4 t = *(const u32x4 *)(x + 16), nn = *(const u32x4 *)(x + 20);
+            v[2] += t.x + t.y + t.z + t.w;
+            v[3] += nn.x + nn.y + nn.z + nn.w;
+        })) {
         if (p.seg && tid == 0) {
             L.out_count[c] = 0u;
             if (L.exc_count) L.exc_count[c] = 0u;
         }
         return;
     }
-
-    // {kept, entries, TTL, NO_NEIGH} of the chunks before this one; chunk 0: of every chunk
-    uint32_t v[4] = {0u, 0u, 0u, 0u};
-    const uint32_t upto = c ? c : nchunk;
-    if (c == 0 || !p.seg) {
-        for (uint32_t s = tid; s < upto; s += BLOCK) {
-            const uint32_t *const x = sc0 + (size_t)s * SW;
-            const u32x4 k = *(const u32x4 *)(x + 8), t = *(const u32x4 *)(x + 16), m = *(const u32x4 *)(x + 20);
-            v[0] += k.x + k.y + k.z + k.w;
-            v[1] += x[12];
-            v[2] += t.x + t.y + t.z + t.w;
-            v[3] += m.x + m.y + m.z + m.w;
-        }
-        block_sum4(v, red, lane, wave);
-    }
-    const u32x4 wk = *(const u32x4 *)(sc + 8);
-    const uint32_t kept_here = wk.x + wk.y + wk.z + wk.w;
     if (c == 0 && tid == 0) {
         __builtin_nontemporal_store(u32x4{v[0], v[1] - v[0], v[2], v[3]}, (u32x4 *)L.status);
         if (!p.seg) {
@@ -211,66 +142,41 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_write(const CopKFwd p)
         }
     }
     if (p.seg && tid == 0) {
-        L.out_count[c] = kept_here;
-        if (L.exc_count) L.exc_count[c] = cnt - kept_here;
+        L.out_count[c] = m.kept_here;
+        if (L.exc_count) L.exc_count[c] = m.cnt - m.kept_here;
     }
-    if ((uint32_t)tid >= cnt) return;
+    if (tid >= m.cnt) return;
 
-    const unsigned long long bits = ((unsigned long long)sc[2 * wave + 1] << 32) | sc[2 * wave];
-    const uint32_t before = (wave > 0 ? wk.x : 0u) + (wave > 1 ? wk.y : 0u) + (wave > 2 ? wk.z : 0u) +
-                            (uint32_t)__popcll(bits & ((1ull << lane) - 1ull));
-    const uint32_t e = L.idx[(size_t)c * BLOCK + tid];
-    if ((bits >> lane) & 1ull) {
-        const size_t base = p.seg ? (size_t)c * BLOCK : (size_t)(c ? v[0] : 0u);
-        L.out_idx[base + before] = e;
+    const uint32_t e = L.h.idx[(size_t)c * BLOCK + tid];
+    if (m.keep) {
+        L.out_idx[mark_base(p.seg, c, v[0]) + m.before] = e;
     } else if (L.exc_idx) {
-        const size_t base = p.seg ? (size_t)c * BLOCK : (size_t)(c ? v[1] - v[0] : 0u);
-        const uint32_t cls = (sc[24 + (tid >> 3)] >> (4 * (tid & 7))) & 0xFu;
-        L.exc_idx[base + ((uint32_t)tid - before)] = min(e, L.n - 1u) | (cls << 28);
+        const uint32_t cls = (sc0[(size_t)c * SW + 24 + (tid >> 3)] >> (4 * (tid & 7))) & 0xFu;
+        L.exc_idx[mark_base(p.seg, c, v[1] - v[0]) + (tid - m.before)] = min(e, L.h.n - 1u) | (cls << 28);
     }
 }
 
 __global__ __launch_bounds__(BLOCK) void cop_fwd_rw(const CopKFwd p)
 {
     __shared__ uint32_t red[4][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKFwdList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t n = L.n;
-    const uint32_t nchunk = (n + BLOCK - 1) / BLOCK;
-
-    // the chunk's entries, its first list position k0, the list's length
-    uint32_t cnt, k0, total;
-    if (p.seg) {
-        uint32_t v[4] = {0u, 0u, 0u, 0u};
-        for (uint32_t s = tid; s < nchunk; s += BLOCK) {
-            const uint32_t x = min(L.count[s], chunk_cap(n, s));
-            v[0] += x;
-            if (s < c) v[1] += x;
-        }
-        block_sum4(v, red, lane, wave);
-        cnt = min(L.count[c], chunk_cap(n, c));
-        total = v[0];
-        k0 = v[1];
-    } else {
-        total = min(L.count[0], n);
-        k0 = c * BLOCK;
-        cnt = total > k0 ? min(total - k0, (uint32_t)BLOCK) : 0u;
-    }
-    const uint32_t W = min(min(L.tx_status[0], L.cap_frames), total);
-    const uint32_t k = k0 + (uint32_t)tid;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const CopKFwdList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    const ChunkAt at = chunk_locate(L.h, p.seg, c, nullptr, red);
+    const uint32_t cnt = at.cnt;
+    const uint32_t W = min(min(L.tx_status[0], L.cap_frames), at.total);
+    const uint32_t k = at.k0 + (uint32_t)tid;
 
     uint32_t cls = 0xFu;   // no frame
     if ((uint32_t)tid < cnt && k < W) {
-        const uint32_t i = min(L.idx[(size_t)c * BLOCK + tid], n - 1u);
-        const unsigned long long at = L.offsets ? (unsigned long long)L.off[k] : (unsigned long long)k * L.slot_bytes;
-        bool is_short = (at & 15ull) || at + 48ull > (unsigned long long)L.cap_bytes;
-        if (L.offsets && L.len[k] < 34u) is_short = true;
+        const uint32_t i = chunk_entry(L.h, c, tid);
+        const unsigned long long fo = L.h.offsets ? (unsigned long long)L.off[k] : (unsigned long long)k * L.slot_bytes;
+        bool is_short = (fo & 15ull) || fo + 48ull > (unsigned long long)L.cap_bytes;
+        if (L.h.offsets && L.len[k] < 34u) is_short = true;
         cls = SHORT;
         u32x4 ent = {0u, 0u, 0u, 0u};
         if (!is_short) {
-            uint8_t *const f = L.frames + at;
+            uint8_t *const f = L.frames + fo;
             const u32x4 p0 = *(const u32x4 *)f, p1 = *(const u32x4 *)(f + 16);
             const uint32_t w8 = p.tab.verify ? *(const uint32_t *)(f + 32) : 0u;
             cls = class_of(p.tab, p0, p1, w8, L.results, i, ent);
@@ -294,7 +200,7 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_rw(const CopKFwd p)
         v[1] = (uint32_t)__popcll(b_pass);
         v[2] = (uint32_t)__popcll(b_any) - v[0] - v[1];
     }
-    block_sum4(v, red, lane, wave);
+    block_sum(v, red);
     if (tid == 0)
         *(u32x4 *)(p.scratch + (size_t)(p.scratch_begin + blockIdx.x) * SW) = u32x4{v[0], v[1], v[2], 0u};
 }
@@ -303,10 +209,10 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_rw(const CopKFwd p)
 __global__ __launch_bounds__(BLOCK) void cop_fwd_rw_status(const CopKFwd p)
 {
     __shared__ uint32_t red[4][4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const CopKFwdList &L = p.l[blockIdx.x];
-    const uint32_t nchunk = (L.n + BLOCK - 1) / BLOCK;
-    const uint32_t *const sc0 = p.scratch + (size_t)(p.scratch_begin + L.chunk_begin) * SW;
+    const uint32_t nchunk = (L.h.n + BLOCK - 1) / BLOCK;
+    const uint32_t *const sc0 = p.scratch + (size_t)(p.scratch_begin + L.h.chunk_begin) * SW;
     uint32_t v[4] = {0u, 0u, 0u, 0u};
     for (uint32_t s = tid; s < nchunk; s += BLOCK) {
         const u32x4 x = *(const u32x4 *)(sc0 + (size_t)s * SW);
@@ -314,7 +220,7 @@ __global__ __launch_bounds__(BLOCK) void cop_fwd_rw_status(const CopKFwd p)
         v[1] += x.y;
         v[2] += x.z;
     }
-    block_sum4(v, red, lane, wave);
+    block_sum(v, red);
     if (tid == 0) __builtin_nontemporal_store(u32x4{v[0], v[1], v[2], 0u}, (u32x4 *)L.status);
 }
 

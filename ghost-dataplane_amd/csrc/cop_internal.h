@@ -244,8 +244,28 @@ int cop_lpm_audit_probes(const cop_lpm_table *t, int form, uint32_t **ips, uint3
  * reason. */
 int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t n_lists, int seg,
                     uint32_t max_batch, const char **why);
+
+/* ---- what the side calls' argument checks share (extents.c) ---------------- */
+/* One memory extent [start, end) of a call, and whether the call writes it. */
+typedef struct {
+    uintptr_t start, end;
+    int written;
+} cop_extent;
+/* appends [p, p + bytes) at v[*k]; a NULL p or no bytes: nothing */
+void cop_extent_put(cop_extent *v, uint32_t *k, const void *p, uint64_t bytes, int written);
+/* what a list call reads of a batch with packets (at most 6 extents): packets
+ * (an IMIX slab: its first 16 bytes), offsets, lens (or NULL), results, lists */
+void cop_extent_put_batch(cop_extent *v, uint32_t *k, const cop_batch *b, const uint32_t *lens, uint32_t n_lists,
+                          int seg);
+/* 1 iff a written extent meets an extent the call reads or, unless
+ * outputs_may_meet, another written one. Sorts v. */
+int cop_extents_clash(cop_extent *v, uint32_t k, int outputs_may_meet);
 /* words of fwd_count a batch of n packets has in that layout */
 uint32_t cop_tx_fwd_count_words(uint32_t n, uint32_t n_lists, int seg);
+/* a packet start of the batch is not 16-byte aligned (pkts, data_off, stride) */
+int cop_batch_misaligned(const cop_batch *b);
+/* a batch of a list call: the pointers a batch with packets needs, and the alignment above */
+int cop_batch_lists_check(const cop_batch *b, const char **why);
 
 /* ---- sketch (sketch.c, cop_sketch.hip) ------------------------------------- */
 /* The argument checks the cop_sketch_* device entry points and the host mirror

@@ -239,6 +239,22 @@ struct CopKLookup {
     const uint32_t *bidx, *bpairs;
 };
 
+// The chunk grid of the side calls (cop_chunk.h): what every forward list of a
+// launch says of itself, the first member of CopKTxList, CopKSkList and
+// CopKFwdList. Workgroup chunk_begin + c serves the list's chunk c:
+// COPK_CHUNK list positions, a segment of a segmented list.
+#define COPK_CHUNK 256
+struct CopKListHead {
+    const uint8_t *pkts;       // batch pkts + data_off
+    const uint32_t *offsets;   // IMIX: byte offset of packet i; slot batches: null
+    const uint32_t *idx;       // the list's first index word (4-byte aligned)
+    const uint32_t *count;     // its length (dense, per vport), or one word per segment
+    uint32_t n;                // the batch's packets: what the list layout holds
+    uint32_t stride;
+    uint32_t chunk_begin;      // first workgroup of this list
+    uint32_t _pad;
+};
+
 // cop_tx_sums / cop_tx_copy (cop_tx.hip): forwarded frames packed into tx
 // bursts (cop_tx_gather). One CopKTxList per forward list (a batch's dense
 // list, one vport's list, or a batch's segments in order), at most
@@ -248,19 +264,13 @@ struct CopKLookup {
 #define COPK_TX_CHUNK 256
 #define COPK_TX_MAX_FRAME 2048u
 struct CopKTxList {
-    const uint8_t *pkts;       // batch pkts + data_off
-    const uint32_t *offsets;   // IMIX: byte offset of packet i; slot batches: null
+    CopKListHead h;
     const uint32_t *lens;      // IMIX: frame length of packet i
-    const uint32_t *idx;       // the list's first index word (4-byte aligned)
-    const uint32_t *count;     // its length (dense, per vport), or one word per segment
     uint8_t *frames;           // 16-byte aligned
     uint32_t *off, *len;       // or null
     uint32_t *status;          // 16-byte aligned, 4 words
-    uint32_t n;                // the batch's packets: what the list layout holds
-    uint32_t stride;
     uint32_t copy_bytes, slot_bytes;   // slot batches
     uint32_t cap_bytes, cap_frames;
-    uint32_t chunk_begin;      // first workgroup of this list
     uint32_t sums_begin;       // IMIX: first word of this list's chunk byte sums in CopKTx::sums
 };
 struct CopKTx {
@@ -304,18 +314,11 @@ struct CopKSkUpdate {
     uint32_t combine;          // equal keys of a workgroup combined in LDS before going to memory (0: timing A/B only)
 };
 struct CopKSkList {
-    const uint8_t *pkts;       // batch pkts + data_off
-    const uint32_t *offsets;
-    const uint32_t *idx;       // the list's first index word
-    const uint32_t *count;     // its length (dense, per vport), or one word per segment
+    CopKListHead h;            // its scratch at (h.chunk_begin + c) * COPK_SK_SCRATCH_WORDS
     uint32_t *out_idx;         // the same position of the output layout
     uint32_t *out_count;
     uint32_t *status;          // 16-byte aligned, 4 words
     unsigned long long threshold;
-    uint32_t n;
-    uint32_t stride;
-    uint32_t chunk_begin;      // first workgroup of this list; its scratch at (chunk_begin + c) * COPK_SK_SCRATCH_WORDS
-    uint32_t _pad;
 };
 struct CopKSkPolice {
     CopKSketch sk;
@@ -369,12 +372,11 @@ struct CopKAead {
 // cop_fwd_mark / cop_fwd_write / cop_fwd_rw / cop_fwd_rw_status (cop_fwd.hip):
 // the L3 forward step (cop_fwd_check, cop_fwd_rewrite). One CopKFwdList per
 // forward list, at most COPK_FWD_MAXL per launch, on the chunk grid of
-// cop_tx.hip: workgroup chunk_begin + c serves chunk c (COPK_FWD_CHUNK list
-// positions) of its list. Scratch per chunk, COPK_FWD_SCRATCH_WORDS words from
-// (scratch_begin + chunk_begin + c): check: words 0..7 the four waves' keep
-// ballots, 8..11 their kept counts, 12 the chunk's entries, 16..19 the waves'
-// COP_FWD_TTL counts, 20..23 their COP_FWD_NO_NEIGH counts, 24..55 the 256
-// 4-bit classes; rewrite: words 0..2 the chunk's {rewritten, PASS, other}.
+// cop_chunk.h. Scratch per chunk, COPK_FWD_SCRATCH_WORDS words from
+// (scratch_begin + chunk_begin + c): check: words 0..12 the mark record,
+// 16..19 the waves' COP_FWD_TTL counts, 20..23 their COP_FWD_NO_NEIGH counts,
+// 24..55 the 256 4-bit classes; rewrite: words 0..2 the chunk's {rewritten,
+// PASS, other}.
 #define COPK_FWD_MAXL 16
 #define COPK_FWD_CHUNK 256
 #define COPK_FWD_SCRATCH_WORDS 56
@@ -386,12 +388,9 @@ struct CopKFwdTab {
     uint32_t _pad;
 };
 struct CopKFwdList {
-    const uint8_t *pkts;       // check: batch pkts + data_off
-    const uint32_t *offsets;   // IMIX batches (check: byte offset of packet i; rewrite: only its being non-null)
+    CopKListHead h;            // pkts, stride: check; offsets: rewrite takes only its being non-null
     const uint32_t *lens;      // check, IMIX: frame length of packet i
     const void *results;       // 8-byte records or null
-    const uint32_t *idx;       // the list's first index word
-    const uint32_t *count;     // its length (dense, per vport), or one word per segment
     uint32_t *out_idx, *out_count;   // check
     uint32_t *exc_idx, *exc_count;   // check, or null
     uint32_t *status;          // 16-byte aligned, 4 words
@@ -399,11 +398,8 @@ struct CopKFwdList {
     const uint32_t *off, *len; // rewrite, IMIX
     const uint32_t *tx_status; // rewrite: the gather's status (word 0: frames written)
     uint32_t *port;            // rewrite, or null
-    uint32_t n;
-    uint32_t stride;           // check
     uint32_t slot_bytes;       // rewrite, slot batches
     uint32_t cap_bytes, cap_frames;   // rewrite
-    uint32_t chunk_begin;      // first workgroup of this list
 };
 struct CopKFwd {
     CopKFwdTab tab;

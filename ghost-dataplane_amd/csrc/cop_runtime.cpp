@@ -386,20 +386,15 @@ struct cop_ctx {
     };
     std::vector<Retired> retired;
     LookupStage lookup_stage[2];       // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
-    // cop_tx_gather / cop_submit_tx: per lane, the IMIX chunk byte sums (allocated at the lane's
-    // first IMIX gather, at the context's worst case) and the event that orders a gather behind the lane
-    uint32_t *tx_sums[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    // the side calls (cop_tx_gather, cop_sketch_*, cop_aead_*, cop_fwd_*): per lane the event that
+    // orders a call behind the lane, and per kind and lane the kernels' scratch (side_scratch:
+    // allocated at the lane's first call of the kind, at the context's worst case): the gather's
+    // IMIX chunk byte sums, the police's and the forward step's chunk records, the MAC waves' counts
     hipEvent_t tx_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    // cop_sketch_*: the context's sketches, and per lane the police scratch (allocated at the
-    // lane's first police, at the context's worst case)
-    std::vector<cop_sketch *> sketches;
-    uint32_t *pol_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    // cop_aead_*: per lane, the MAC waves' status counts (allocated at the lane's first call)
-    uint32_t *aead_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    // cop_neigh_* / cop_fwd_*: the context's neighbour tables, and per lane the check's and the
-    // rewrite's chunk scratch (allocated at the lane's first call, at the context's worst case)
-    std::vector<cop_neigh *> neighs;
-    uint32_t *fwd_scratch[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
+    enum { SIDE_TX_SUMS, SIDE_POLICE, SIDE_AEAD, SIDE_FWD, SIDE_KINDS };
+    uint32_t *side_scratch[SIDE_KINDS][MAX_LANES] = {};
+    std::vector<cop_sketch *> sketches;   // cop_sketch_*: the context's sketches
+    std::vector<cop_neigh *> neighs;      // cop_neigh_* / cop_fwd_*: its neighbour tables
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -585,8 +580,9 @@ void cop_destroy(cop_ctx *c)
         if (S.done) (void)hipEventDestroy(S.done);
     }
     if (c->live_done) (void)hipEventDestroy(c->live_done);
-    for (auto &p : c->tx_sums)
-        if (p) (void)hipFree(p);
+    for (auto &kind : c->side_scratch)
+        for (uint32_t *p : kind)
+            if (p) (void)hipFree(p);
     for (auto &e : c->tx_ev)
         if (e) (void)hipEventDestroy(e);
     sketch_free_all(c);
@@ -3875,15 +3871,64 @@ int cop_lookup_audit(cop_ctx *c, uint32_t stage, const cop_lpm_table *tab, cop_a
     return rc;
 }
 
-// ---- tx gather (cop_tx.hip) -------------------------------------------------
-// cop_tx_gather / cop_submit_tx: every forward list of the batches becomes one
-// CopKTxList; a launch carries up to COPK_TX_MAXL of them (its parameters are
-// kernel arguments, so nothing the host could rewrite under queued work), all
-// of one kind (slot or IMIX). IMIX launches use the lane's chunk-sum scratch,
-// allocated once at the worst case the context admits (max_batches x
-// ceil(max_batch / 256) x lists per batch words) and freed by cop_destroy
-// alone: launches of one lane run in order, so the next gather's pre-pass
-// overwrites the sums only after this one's copy kernel has read them.
+// ---- side calls: what cop_tx_gather, cop_sketch_*, cop_aead_* and cop_fwd_* share ----
+// Their launch parameters are kernel arguments, so nothing the host could
+// rewrite under queued work. Ordering (side_run): the next launch lane, behind
+// every busy lane by events; beside a poll-mode kernel pause, run on the side
+// stream, sync, resume. Scratch (side_scratch): one buffer per kind and lane,
+// allocated once at the worst case the context admits and freed by cop_destroy
+// alone, never grown: launches of one lane run in order, so the next call of
+// the kind overwrites it only after this one's last kernel has read it.
+
+// Between pmd_pause and pmd_resume: op() queues on c->stream (0, or an error it has set), then the
+// stream is drained; `fail` is the error of a drain that failed.
+static int paused_op(cop_ctx *c, const char *fail, const std::function<int()> &op)
+{
+    if (int rc = pmd_pause(c)) return rc;
+    int rc = op();
+    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s", fail);
+    const int rrc = pmd_resume(c);
+    return rc ? rc : rrc;
+}
+
+// Runs launch(lane, stream) as a side call: asynchronous on the next lane behind every lane's queued
+// work, or synchronous between pmd_pause and pmd_resume on the side stream.
+static int side_run(cop_ctx *c, const char *what, const std::function<int(int, hipStream_t)> &launch)
+{
+    HIPCHK(c, hipSetDevice(c->device));
+    if (c->pmd) {
+        char fail[64];
+        snprintf(fail, sizeof(fail), "%s sync", what);
+        return paused_op(c, fail, [&]() -> int { return launch(0, c->stream); });
+    }
+    const int lane = c->next_lane;
+    Lane &L = c->lane[lane];
+    c->next_lane = (c->next_lane + 1) % c->n_lanes;
+    // live_order_begin's event pattern; a lane with nothing in flight has nothing to be ordered behind
+    for (int l = 0; l < c->n_lanes; l++) {
+        if (l == lane || hipStreamQuery(c->lane[l].s) == hipSuccess) continue;
+        if (!c->tx_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->tx_ev[l], hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->tx_ev[l], c->lane[l].s));
+        HIPCHK(c, hipStreamWaitEvent(L.s, c->tx_ev[l], 0));
+    }
+    (void)hipGetLastError();   // a busy lane's hipErrorNotReady is no launch error
+    return launch(lane, L.s);
+}
+
+static int side_scratch(cop_ctx *c, int kind, int lane, size_t bytes, uint32_t **out)
+{
+    uint32_t *&p = c->side_scratch[kind][lane];
+    if (!p) HIPCHK(c, hipMalloc(&p, bytes));
+    *out = p;
+    return 0;
+}
+
+// bytes of `words` words per chunk of every list the context admits in one call
+static size_t chunk_scratch_bytes(const cop_ctx *c, uint32_t n_lists, uint32_t words)
+{
+    return (size_t)c->cfg.max_batches * ((c->cfg.max_batch + COPK_CHUNK - 1) / COPK_CHUNK) * n_lists * words * 4;
+}
+
 static int tx_layout(cop_ctx *c, uint32_t *n_lists, int *seg)
 {
     if (c->cfg.flags & COP_CFG_NO_COMPACT)
@@ -3893,22 +3938,77 @@ static int tx_layout(cop_ctx *c, uint32_t *n_lists, int *seg)
     return 0;
 }
 
+// What a call over the batches' forward lists checks first: the context's list layout, nb, and
+// validate(n_lists, seg, &why), the call's argument check (cop_internal.h).
+static int list_call_check(cop_ctx *c, const char *what, uint32_t nb, uint32_t *n_lists, int *seg,
+                           const std::function<int(uint32_t, int, const char **)> &validate)
+{
+    if (int rc = tx_layout(c, n_lists, seg)) return rc;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "%s: nb %u > max_batches", what, nb);
+    const char *why = "";
+    if (int rc = validate(*n_lists, *seg, &why)) return set_err(c, rc, "%s: %s", what, why);
+    return 0;
+}
+
+// list q of batch b, its first workgroup chunk_begin
+static void list_head(CopKListHead &h, const cop_batch &b, uint32_t q, uint32_t chunk_begin)
+{
+    h.pkts = (const uint8_t *)b.pkts + b.data_off;
+    h.offsets = b.offsets;
+    h.idx = b.n ? b.fwd_idx + (size_t)q * b.n : nullptr;
+    h.count = b.n ? b.fwd_count + q : nullptr;
+    h.n = b.n;
+    h.stride = b.stride;
+    h.chunk_begin = chunk_begin;
+}
+
+// Every list of every batch with packets into p (a CopKSkPolice or CopKFwd with scratch), launched
+// whenever p holds maxl lists and at the end; fill(list, batch index, q) sets what follows the head.
+extern "C++" template <typename P, typename F>
+static int pack_lists(cop_ctx *c, const char *what, P &p, uint32_t maxl, hipError_t (*launch)(const P *, hipStream_t),
+                      hipStream_t s, const cop_batch *batches, uint32_t nb, uint32_t n_lists, F fill)
+{
+    auto flush = [&]() -> int {
+        const hipError_t e = launch(&p, s);
+        p.scratch_begin += p.nchunks;   // within the scratch: nb <= max_batches, n <= max_batch
+        p.nl = 0;
+        p.nchunks = 0;
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "%s launch: %s", what, hipGetErrorString(e));
+    };
+    for (uint32_t i = 0; i < nb; i++) {
+        const cop_batch &b = batches[i];
+        if (!b.n) continue;
+        for (uint32_t q = 0; q < n_lists; q++) {
+            if (p.nl == maxl)
+                if (int rc = flush()) return rc;
+            auto &l = p.l[p.nl++];
+            memset(&l, 0, sizeof(l));
+            list_head(l.h, b, q, p.nchunks);
+            fill(l, i, q);
+            p.nchunks += (b.n + COPK_CHUNK - 1) / COPK_CHUNK;
+        }
+    }
+    return flush();
+}
+
+// ---- tx gather (cop_tx.hip) -------------------------------------------------
+// cop_tx_gather / cop_submit_tx: every forward list of the batches becomes one
+// CopKTxList; a launch carries up to COPK_TX_MAXL of them, all of one kind
+// (slot or IMIX). IMIX launches use the lane's chunk-sum scratch, one word per
+// chunk. The packing loop is the gather's own: an empty batch still gets one
+// chunk, a change of kind ends a launch, and the sums have an offset of their
+// own, which pack_lists would only carry as flags.
 static int tx_check(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t *n_lists,
                     int *seg)
 {
-    if (int rc = tx_layout(c, n_lists, seg)) return rc;
-    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "tx gather: nb %u > max_batches", nb);
-    const char *why = "";
-    if (int rc = cop_tx_validate(batches, tx, nb, *n_lists, *seg, c->cfg.max_batch, &why))
-        return set_err(c, rc, "tx gather: %s", why);
-    return 0;
+    return list_call_check(c, "tx gather", nb, n_lists, seg, [&](uint32_t nl, int sg, const char **why) {
+        return cop_tx_validate(batches, tx, nb, nl, sg, c->cfg.max_batch, why);
+    });
 }
 
 static int tx_launch(cop_ctx *c, int lane, hipStream_t s, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb,
                      uint32_t n_lists, int seg)
 {
-    const uint32_t cpb = (c->cfg.max_batch + COPK_TX_CHUNK - 1) / COPK_TX_CHUNK;
-    const size_t sums_words = (size_t)c->cfg.max_batches * cpb * n_lists;
     CopKTx p;
     memset(&p, 0, sizeof(p));
     p.seg = seg ? 1u : 0u;
@@ -3925,9 +4025,8 @@ static int tx_launch(cop_ctx *c, int lane, hipStream_t s, const cop_batch *batch
         const cop_batch &b = batches[i];
         const cop_tx_desc &t = tx[i];
         const int imix = b.offsets != nullptr;
-        if (imix && !c->tx_sums[lane]) {
-            HIPCHK(c, hipMalloc(&c->tx_sums[lane], sums_words * 4));
-        }
+        if (imix)
+            if (int rc = side_scratch(c, cop_ctx::SIDE_TX_SUMS, lane, chunk_scratch_bytes(c, n_lists, 1), &p.sums)) return rc;
         const uint32_t chunks = b.n ? (b.n + COPK_TX_CHUNK - 1) / COPK_TX_CHUNK : 1u;
         for (uint32_t q = 0; q < n_lists; q++) {
             if (p.nl == COPK_TX_MAXL || (p.nl && kind != imix))
@@ -3935,26 +4034,19 @@ static int tx_launch(cop_ctx *c, int lane, hipStream_t s, const cop_batch *batch
             kind = imix;
             const cop_tx_burst &o = t.out[q];
             CopKTxList &l = p.l[p.nl++];
-            l.pkts = (const uint8_t *)b.pkts + b.data_off;
-            l.offsets = b.offsets;
+            list_head(l.h, b, q, p.nchunks);
             l.lens = t.lens;
-            l.idx = b.n ? b.fwd_idx + (size_t)q * b.n : nullptr;
-            l.count = b.n ? b.fwd_count + q : nullptr;
             l.frames = (uint8_t *)o.frames;
             l.off = o.off;
             l.len = o.len;
             l.status = o.status;
-            l.n = b.n;
-            l.stride = b.stride;
             l.copy_bytes = t.copy_bytes;
             l.slot_bytes = t.slot_bytes;
             l.cap_bytes = (uint32_t)o.cap_bytes;
             l.cap_frames = o.cap_frames;
-            l.chunk_begin = p.nchunks;
             l.sums_begin = sums_used;
             p.nchunks += chunks;
-            if (imix) sums_used += chunks;   // <= sums_words: nb <= max_batches, n <= max_batch
-            p.sums = c->tx_sums[lane];
+            if (imix) sums_used += chunks;   // within the scratch: nb <= max_batches, n <= max_batch
         }
     }
     return flush();
@@ -3967,28 +4059,9 @@ int cop_tx_gather(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, u
     uint32_t n_lists = 1;
     int seg = 0;
     if (int rc = tx_check(c, batches, tx, nb, &n_lists, &seg)) return rc;
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->pmd) {
-        // as cop_lookup_bulk: pause the poll-mode kernel, gather on the free GPU, relaunch it
-        if (int rc = pmd_pause(c)) return rc;
-        int rc = tx_launch(c, 0, c->stream, batches, tx, nb, n_lists, seg);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "tx gather sync");
-        const int rrc = pmd_resume(c);
-        return rc ? rc : rrc;
-    }
-    const int lane = c->next_lane;
-    Lane &L = c->lane[lane];
-    c->next_lane = (c->next_lane + 1) % c->n_lanes;
-    // behind everything queued so far on every other lane (live_order_begin's event pattern);
-    // a lane with nothing in flight has nothing to be ordered behind
-    for (int l = 0; l < c->n_lanes; l++) {
-        if (l == lane || hipStreamQuery(c->lane[l].s) == hipSuccess) continue;
-        if (!c->tx_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->tx_ev[l], hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->tx_ev[l], c->lane[l].s));
-        HIPCHK(c, hipStreamWaitEvent(L.s, c->tx_ev[l], 0));
-    }
-    (void)hipGetLastError();   // a busy lane's hipErrorNotReady is no launch error
-    return tx_launch(c, lane, L.s, batches, tx, nb, n_lists, seg);
+    return side_run(c, "tx gather", [&](int lane, hipStream_t s) -> int {
+        return tx_launch(c, lane, s, batches, tx, nb, n_lists, seg);
+    });
 }
 
 int cop_submit_tx(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb)
@@ -4006,13 +4079,66 @@ int cop_submit_tx(cop_ctx *c, const cop_batch *batches, const cop_tx_desc *tx, u
     return tx_launch(c, lane, L.s, batches, tx, nb, n_lists, seg);
 }
 
+// ---- device objects: what sketches and neighbour tables share ----------------
+// A device object is a host struct in a registry of its context that owns one
+// device allocation.
+extern "C++" {
+template <typename T>
+static int devobj_of(cop_ctx *c, const std::vector<T *> &reg, const T *obj, const char *what, const char *kind)
+{
+    if (!obj || std::find(reg.begin(), reg.end(), obj) == reg.end())
+        return set_err(c, -EINVAL, "%s: not a %s of this context", what, kind);
+    return 0;
+}
+
+// Allocates and zeroes the object's `bytes` of device memory (*dptr, a member of *obj) and registers
+// it, or deletes it. Synchronous, and touches nothing queued work uses; a poll-mode kernel is paused
+// for it as for every side call. The errors read "<what>: <n> <bytes_of> bytes", "<what>: zeroing <zeroed>".
+template <typename T, typename D>
+static int devobj_create(cop_ctx *c, std::vector<T *> &reg, T *obj, D **dptr, size_t bytes, const char *what,
+                         const char *bytes_of, const char *zeroed, T **out)
+{
+    char fail[64];
+    snprintf(fail, sizeof(fail), "%s: zeroing %s", what, zeroed);
+    *dptr = nullptr;
+    const int rc = paused_op(c, fail, [&]() -> int {
+        if (hipMalloc(dptr, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            *dptr = nullptr;
+            return set_err(c, -ENOMEM, "%s: %llu %s bytes", what, (unsigned long long)bytes, bytes_of);
+        }
+        return hipMemsetAsync(*dptr, 0, bytes, c->stream) == hipSuccess ? 0 : set_err(c, -EIO, "%s", fail);
+    });
+    if (rc) {
+        if (*dptr) (void)hipFree(*dptr);
+        delete obj;
+        return rc;
+    }
+    reg.push_back(obj);
+    *out = obj;
+    return 0;
+}
+
+// mem(obj): the object's device memory, asked for once obj is known to be registered
+template <typename T, typename F>
+static int devobj_destroy(cop_ctx *c, std::vector<T *> &reg, T *obj, const char *what, const char *kind, F mem)
+{
+    if (int rc = devobj_of(c, reg, obj, what, kind)) return rc;
+    if (int rc = sync_lanes(c)) return rc;   // queued work may use the memory
+    // beside a poll-mode kernel every side call has completed on return, and hipFree must not wait for it
+    if (int rc = pmd_pause(c)) return rc;
+    (void)hipFree(mem(obj));
+    const int rrc = pmd_resume(c);
+    reg.erase(std::find(reg.begin(), reg.end(), obj));
+    delete obj;
+    return rrc;
+}
+}  // extern "C++"
+
 // ---- sketch (cop_sketch.hip) ------------------------------------------------
 // A sketch is its configuration, the hash parameters derived from it (so host
 // and device agree bit for bit) and rows << log2_cols u64 words of device
-// memory. The launch parameters are kernel arguments, so nothing the host
-// could rewrite under queued work. Ordering is cop_tx_gather's: the next
-// launch lane, behind every busy lane by events; beside a poll-mode kernel
-// pause, run on the side stream, sync, resume.
+// memory.
 struct cop_sketch {
     cop_ctx *owner;
     cop_sketch_config cfg;
@@ -4027,47 +4153,11 @@ static void sketch_free_all(cop_ctx *c)
         delete s;
     }
     c->sketches.clear();
-    for (auto &p : c->pol_scratch) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
-    for (auto &p : c->aead_scratch) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
 }
 
 static int sketch_of(cop_ctx *c, const cop_sketch *sk, const char *what)
 {
-    if (!sk || std::find(c->sketches.begin(), c->sketches.end(), sk) == c->sketches.end())
-        return set_err(c, -EINVAL, "%s: not a sketch of this context", what);
-    return 0;
-}
-
-// Runs launch(lane, stream) as a side call: asynchronous on the next lane behind every lane's queued
-// work, or synchronous between pmd_pause and pmd_resume on the side stream.
-static int sketch_run(cop_ctx *c, const char *what, const std::function<int(int, hipStream_t)> &launch)
-{
-    HIPCHK(c, hipSetDevice(c->device));
-    if (c->pmd) {
-        if (int rc = pmd_pause(c)) return rc;
-        int rc = launch(0, c->stream);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s sync", what);
-        const int rrc = pmd_resume(c);
-        return rc ? rc : rrc;
-    }
-    const int lane = c->next_lane;
-    Lane &L = c->lane[lane];
-    c->next_lane = (c->next_lane + 1) % c->n_lanes;
-    // live_order_begin's event pattern; a lane with nothing in flight has nothing to be ordered behind
-    for (int l = 0; l < c->n_lanes; l++) {
-        if (l == lane || hipStreamQuery(c->lane[l].s) == hipSuccess) continue;
-        if (!c->tx_ev[l]) HIPCHK(c, hipEventCreateWithFlags(&c->tx_ev[l], hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->tx_ev[l], c->lane[l].s));
-        HIPCHK(c, hipStreamWaitEvent(L.s, c->tx_ev[l], 0));
-    }
-    (void)hipGetLastError();   // a busy lane's hipErrorNotReady is no launch error
-    return launch(lane, L.s);
+    return devobj_of(c, c->sketches, sk, what, "sketch");
 }
 
 int cop_sketch_create(cop_ctx *c, const cop_sketch_config *cfg, cop_sketch **out)
@@ -4087,44 +4177,13 @@ int cop_sketch_create(cop_ctx *c, const cop_sketch_config *cfg, cop_sketch **out
     s->k.col_shift = 32u - cfg->log2_cols;
     s->k.key_shift = 32u - cfg->key_depth;
     s->k.dst = cfg->key == COP_SKETCH_KEY_DST;
-    // the allocation and the zeroing are synchronous and touch nothing queued work uses; a
-    // poll-mode kernel is paused for them as for every sketch call
-    if (int rc = pmd_pause(c)) {
-        delete s;
-        return rc;
-    }
-    int rc = 0;
-    if (hipMalloc(&s->k.ctr, s->words * 8) != hipSuccess) {
-        (void)hipGetLastError();
-        s->k.ctr = nullptr;
-        rc = set_err(c, -ENOMEM, "sketch: %llu counter bytes", (unsigned long long)s->words * 8);
-    } else if (hipMemsetAsync(s->k.ctr, 0, s->words * 8, c->stream) != hipSuccess ||
-               hipStreamSynchronize(c->stream) != hipSuccess) {
-        rc = set_err(c, -EIO, "sketch: zeroing the counters");
-    }
-    const int rrc = pmd_resume(c);
-    if (rc || rrc) {
-        if (s->k.ctr) (void)hipFree(s->k.ctr);
-        delete s;
-        return rc ? rc : rrc;
-    }
-    c->sketches.push_back(s);
-    *out = s;
-    return 0;
+    return devobj_create(c, c->sketches, s, &s->k.ctr, s->words * 8, "sketch", "counter", "the counters", out);
 }
 
 int cop_sketch_destroy(cop_ctx *c, cop_sketch *sk)
 {
     if (!c) return -EINVAL;
-    if (int rc = sketch_of(c, sk, "sketch_destroy")) return rc;
-    if (int rc = sync_lanes(c)) return rc;   // queued work may use the counters
-    // beside a poll-mode kernel every sketch call has completed on return, and hipFree must not wait for it
-    if (int rc = pmd_pause(c)) return rc;
-    (void)hipFree(sk->k.ctr);
-    const int rrc = pmd_resume(c);
-    c->sketches.erase(std::find(c->sketches.begin(), c->sketches.end(), sk));
-    delete sk;
-    return rrc;
+    return devobj_destroy(c, c->sketches, sk, "sketch_destroy", "sketch", [](cop_sketch *s) { return s->k.ctr; });
 }
 
 int cop_sketch_update(cop_ctx *c, cop_sketch *sk, const cop_batch *batches, uint32_t nb, uint32_t verdict_mask)
@@ -4137,7 +4196,7 @@ int cop_sketch_update(cop_ctx *c, cop_sketch *sk, const cop_batch *batches, uint
     if (int rc = cop_sketch_update_validate(batches, nb, verdict_mask, c->cfg.max_batch, &why))
         return set_err(c, rc, "sketch_update: %s", why);
     static const bool combine = !(getenv("COP_SKETCH_COMBINE") && !strcmp(getenv("COP_SKETCH_COMBINE"), "0"));
-    return sketch_run(c, "sketch_update", [&](int, hipStream_t s) -> int {
+    return side_run(c, "sketch_update", [&](int, hipStream_t s) -> int {
         CopKSkUpdate p;
         memset(&p, 0, sizeof(p));
         p.sk = sk->k;
@@ -4175,7 +4234,7 @@ int cop_sketch_query(cop_ctx *c, const cop_sketch *sk, const uint32_t *ips, uint
     const char *why = "";
     if (int rc = cop_sketch_query_validate(&sk->cfg, sk->k.ctr, ips, n, out, &why))
         return set_err(c, rc, "sketch_query: %s", why);
-    return sketch_run(c, "sketch_query", [&](int, hipStream_t s) -> int {
+    return side_run(c, "sketch_query", [&](int, hipStream_t s) -> int {
         const hipError_t e = copk_sketch_query_launch(&sk->k, ips, n, (unsigned long long *)out, s);
         return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_query launch: %s", hipGetErrorString(e));
     });
@@ -4186,7 +4245,7 @@ int cop_sketch_decay(cop_ctx *c, cop_sketch *sk, uint32_t shift)
     if (!c) return -EINVAL;
     if (int rc = sketch_of(c, sk, "sketch_decay")) return rc;
     if (shift < 1 || shift > 64) return set_err(c, -EINVAL, "sketch_decay: shift %u not in 1..64", shift);
-    return sketch_run(c, "sketch_decay", [&](int, hipStream_t s) -> int {
+    return side_run(c, "sketch_decay", [&](int, hipStream_t s) -> int {
         const hipError_t e = copk_sketch_decay_launch(&sk->k, shift, s);
         return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_decay launch: %s", hipGetErrorString(e));
     });
@@ -4200,53 +4259,25 @@ int cop_sketch_police(cop_ctx *c, const cop_sketch *sk, const cop_batch *batches
     if (nb == 0) return 0;
     uint32_t n_lists = 1;
     int seg = 0;
-    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
-    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "sketch_police: nb %u > max_batches", nb);
-    const char *why = "";
-    if (int rc = cop_sketch_police_validate(&sk->cfg, sk->k.ctr, batches, pol, nb, n_lists, seg, c->cfg.max_batch, &why))
-        return set_err(c, rc, "sketch_police: %s", why);
-    // the lane's scratch: one record per chunk at the worst case the context admits, freed by
-    // cop_destroy alone; launches of one lane run in order, so the next police overwrites it only
-    // after this one's second kernel has read it
-    const uint32_t cpb = (c->cfg.max_batch + COPK_SK_CHUNK - 1) / COPK_SK_CHUNK;
-    const size_t scratch_words = (size_t)c->cfg.max_batches * cpb * n_lists * COPK_SK_SCRATCH_WORDS;
-    return sketch_run(c, "sketch_police", [&](int lane, hipStream_t s) -> int {
-        if (!c->pol_scratch[lane]) HIPCHK(c, hipMalloc(&c->pol_scratch[lane], scratch_words * 4));
+    if (int rc = list_call_check(c, "sketch_police", nb, &n_lists, &seg, [&](uint32_t nl, int sg, const char **why) {
+            return cop_sketch_police_validate(&sk->cfg, sk->k.ctr, batches, pol, nb, nl, sg, c->cfg.max_batch, why);
+        }))
+        return rc;
+    return side_run(c, "sketch_police", [&](int lane, hipStream_t s) -> int {
         CopKSkPolice p;
         memset(&p, 0, sizeof(p));
         p.sk = sk->k;
         p.seg = seg ? 1u : 0u;
-        p.scratch = c->pol_scratch[lane];
-        auto flush = [&]() -> int {
-            const hipError_t e = copk_sketch_police_launch(&p, s);
-            p.scratch_begin += p.nchunks;   // <= max_batches * cpb * n_lists: nb <= max_batches, n <= max_batch
-            p.nl = 0;
-            p.nchunks = 0;
-            return e == hipSuccess ? 0 : set_err(c, -EIO, "sketch_police launch: %s", hipGetErrorString(e));
-        };
-        for (uint32_t i = 0; i < nb; i++) {
-            const cop_batch &b = batches[i];
-            if (!b.n) continue;
-            const uint32_t chunks = (b.n + COPK_SK_CHUNK - 1) / COPK_SK_CHUNK;
-            for (uint32_t q = 0; q < n_lists; q++) {
-                if (p.nl == COPK_SK_MAXL)
-                    if (int rc = flush()) return rc;
-                CopKSkList &l = p.l[p.nl++];
-                l.pkts = (const uint8_t *)b.pkts + b.data_off;
-                l.offsets = b.offsets;
-                l.idx = b.fwd_idx + (size_t)q * b.n;
-                l.count = b.fwd_count + q;
-                l.out_idx = pol[i].out_idx + (size_t)q * b.n;
-                l.out_count = pol[i].out_count + q;
-                l.status = pol[i].status + 4 * q;
-                l.threshold = pol[i].threshold;
-                l.n = b.n;
-                l.stride = b.stride;
-                l.chunk_begin = p.nchunks;
-                p.nchunks += chunks;
-            }
-        }
-        return flush();
+        if (int rc = side_scratch(c, cop_ctx::SIDE_POLICE, lane, chunk_scratch_bytes(c, n_lists, COPK_SK_SCRATCH_WORDS),
+                                  &p.scratch))
+            return rc;
+        return pack_lists(c, "sketch_police", p, COPK_SK_MAXL, copk_sketch_police_launch, s, batches, nb, n_lists,
+                          [&](CopKSkList &l, uint32_t i, uint32_t q) {
+                              l.out_idx = pol[i].out_idx + (size_t)q * batches[i].n;
+                              l.out_count = pol[i].out_count + q;
+                              l.status = pol[i].status + 4 * q;
+                              l.threshold = pol[i].threshold;
+                          });
     });
 }
 
@@ -4257,13 +4288,12 @@ int cop_sketch_read(cop_ctx *c, const cop_sketch *sk, uint64_t *out, uint64_t ca
     if (!out) return set_err(c, -EINVAL, "sketch_read: null pointer");
     if (cap_words < sk->words) return set_err(c, -ENOSPC, "sketch_read: %llu words needed", (unsigned long long)sk->words);
     if (int rc = sync_lanes(c)) return rc;
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = 0;
-    if (hipMemcpyAsync(out, sk->k.ctr, sk->words * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        rc = set_err(c, -EIO, "sketch_read: copy failed");
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc ? rrc : (int)sk->words;
+    const char *fail = "sketch_read: copy failed";
+    const int rc = paused_op(c, fail, [&]() -> int {
+        const hipError_t e = hipMemcpyAsync(out, sk->k.ctr, sk->words * 8, hipMemcpyDeviceToHost, c->stream);
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "%s", fail);
+    });
+    return rc ? rc : (int)sk->words;
 }
 
 int cop_sketch_device_ptr(cop_ctx *c, const cop_sketch *sk, void **dptr, uint64_t *words)
@@ -4280,7 +4310,7 @@ int cop_sketch_device_ptr(cop_ctx *c, const cop_sketch *sk, void **dptr, uint64_
 // cop_aead_seal / cop_aead_open / cop_poly1305_bulk: every burst with frames
 // becomes one CopKAeBurst; a launch carries up to COPK_AE_MAXB of them with the
 // key, all as kernel arguments, so there is no device object and nothing the
-// host could rewrite under queued work. Ordering is sketch_run's. The lane's
+// host could rewrite under queued work. Ordering is side_run's. The lane's
 // scratch holds one 16-byte record per wave of the MAC kernel at the worst case
 // the context admits (max_batches x ceil(max_batch / 256) workgroups), freed by
 // cop_destroy alone: launches of one lane run in order, so the next call's MAC
@@ -4299,12 +4329,11 @@ static int aead_run(cop_ctx *c, const char *what, uint32_t mode, const cop_aead_
     if (!live) return 0;
     const size_t scratch_bytes =
         (size_t)c->cfg.max_batches * ((c->cfg.max_batch + COPK_AE_BLOCK - 1) / COPK_AE_BLOCK) * (COPK_AE_BLOCK / 64) * 16;
-    return sketch_run(c, what, [&](int lane, hipStream_t s) -> int {
-        if (!c->aead_scratch[lane]) HIPCHK(c, hipMalloc(&c->aead_scratch[lane], scratch_bytes));
+    return side_run(c, what, [&](int lane, hipStream_t s) -> int {
         CopKAead p;
         memset(&p, 0, sizeof(p));
         p.mode = mode;
-        p.scratch = c->aead_scratch[lane];
+        if (int rc = side_scratch(c, cop_ctx::SIDE_AEAD, lane, scratch_bytes, &p.scratch)) return rc;
         if (key) {
             memcpy(p.key, key->key, 32);    // the words are little-endian, as the host is
             memcpy(&p.salt, key->salt, 4);
@@ -4371,7 +4400,7 @@ int cop_poly1305_bulk(cop_ctx *c, const cop_aead_burst *burst, const uint8_t *ot
 // and cop_fwd_rewrite turn every forward list of the batches into one
 // CopKFwdList; a launch carries up to COPK_FWD_MAXL of them with the table's
 // description, all as kernel arguments, so nothing the host could rewrite
-// under queued work. Ordering is sketch_run's. The lane's scratch holds
+// under queued work. Ordering is side_run's. The lane's scratch holds
 // COPK_FWD_SCRATCH_WORDS words per chunk at the worst case the context admits,
 // freed by cop_destroy alone: launches of one lane run in order, so the next
 // call's first kernel overwrites it only after this call's second has read it.
@@ -4388,17 +4417,11 @@ static void neigh_free_all(cop_ctx *c)
         delete g;
     }
     c->neighs.clear();
-    for (auto &p : c->fwd_scratch) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    }
 }
 
 static int neigh_of(cop_ctx *c, const cop_neigh *g, const char *what)
 {
-    if (!g || std::find(c->neighs.begin(), c->neighs.end(), g) == c->neighs.end())
-        return set_err(c, -EINVAL, "%s: not a neighbour table of this context", what);
-    return 0;
+    return devobj_of(c, c->neighs, g, what, "neighbour table");
 }
 
 int cop_neigh_create(cop_ctx *c, uint32_t n_entries, cop_neigh **out)
@@ -4408,32 +4431,8 @@ int cop_neigh_create(cop_ctx *c, uint32_t n_entries, cop_neigh **out)
     HIPCHK(c, hipSetDevice(c->device));
     cop_neigh *g = new cop_neigh();
     g->owner = c;
-    g->entries = nullptr;
     g->n_entries = n_entries;
-    const size_t bytes = (size_t)n_entries * 16;
-    // as cop_sketch_create: synchronous, nothing queued work uses, a poll-mode kernel paused
-    if (int rc = pmd_pause(c)) {
-        delete g;
-        return rc;
-    }
-    int rc = 0;
-    if (hipMalloc(&g->entries, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        g->entries = nullptr;
-        rc = set_err(c, -ENOMEM, "neigh: %llu table bytes", (unsigned long long)bytes);
-    } else if (hipMemsetAsync(g->entries, 0, bytes, c->stream) != hipSuccess ||
-               hipStreamSynchronize(c->stream) != hipSuccess) {
-        rc = set_err(c, -EIO, "neigh: zeroing the table");
-    }
-    const int rrc = pmd_resume(c);
-    if (rc || rrc) {
-        if (g->entries) (void)hipFree(g->entries);
-        delete g;
-        return rc ? rc : rrc;
-    }
-    c->neighs.push_back(g);
-    *out = g;
-    return 0;
+    return devobj_create(c, c->neighs, g, &g->entries, (size_t)n_entries * 16, "neigh", "table", "the table", out);
 }
 
 int cop_neigh_set(cop_ctx *c, cop_neigh *g, uint32_t first, uint32_t count, const cop_neigh_entry *host_entries)
@@ -4448,27 +4447,18 @@ int cop_neigh_set(cop_ctx *c, cop_neigh *g, uint32_t first, uint32_t count, cons
     HIPCHK(c, hipSetDevice(c->device));
     // a poll-mode kernel is paused for the copy: it holds every workgroup slot it may use, and a copy
     // the runtime does with a kernel of its own would wait beside it until its idle exit
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = 0;
-    if (hipMemcpyAsync(g->entries + 4 * (size_t)first, host_entries, (size_t)count * 16, hipMemcpyHostToDevice,
-                       c->stream) != hipSuccess ||
-        hipStreamSynchronize(c->stream) != hipSuccess)
-        rc = set_err(c, -EIO, "neigh_set: copy failed");
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
+    const char *fail = "neigh_set: copy failed";
+    return paused_op(c, fail, [&]() -> int {
+        const hipError_t e = hipMemcpyAsync(g->entries + 4 * (size_t)first, host_entries, (size_t)count * 16,
+                                            hipMemcpyHostToDevice, c->stream);
+        return e == hipSuccess ? 0 : set_err(c, -EIO, "%s", fail);
+    });
 }
 
 int cop_neigh_destroy(cop_ctx *c, cop_neigh *g)
 {
     if (!c) return -EINVAL;
-    if (int rc = neigh_of(c, g, "neigh_destroy")) return rc;
-    if (int rc = sync_lanes(c)) return rc;   // queued work may use the table
-    if (int rc = pmd_pause(c)) return rc;    // hipFree must not wait for a poll-mode kernel
-    (void)hipFree(g->entries);
-    const int rrc = pmd_resume(c);
-    c->neighs.erase(std::find(c->neighs.begin(), c->neighs.end(), g));
-    delete g;
-    return rrc;
+    return devobj_destroy(c, c->neighs, g, "neigh_destroy", "neighbour table", [](cop_neigh *t) { return t->entries; });
 }
 
 int cop_neigh_device_ptr(cop_ctx *c, const cop_neigh *g, void **dptr, uint32_t *n_entries)
@@ -4486,10 +4476,7 @@ static int fwd_run(cop_ctx *c, const char *what, const cop_neigh *g, const cop_f
                    uint32_t nb, uint32_t n_lists, int seg, bool rewrite,
                    const std::function<void(CopKFwdList &, uint32_t, uint32_t)> &fill)
 {
-    const uint32_t cpb = (c->cfg.max_batch + COPK_FWD_CHUNK - 1) / COPK_FWD_CHUNK;
-    const size_t scratch_words = (size_t)c->cfg.max_batches * cpb * n_lists * COPK_FWD_SCRATCH_WORDS;
-    return sketch_run(c, what, [&](int lane, hipStream_t s) -> int {
-        if (!c->fwd_scratch[lane]) HIPCHK(c, hipMalloc(&c->fwd_scratch[lane], scratch_words * 4));
+    return side_run(c, what, [&](int lane, hipStream_t s) -> int {
         CopKFwd p;
         memset(&p, 0, sizeof(p));
         p.tab.entries = g->entries;
@@ -4497,36 +4484,14 @@ static int fwd_run(cop_ctx *c, const char *what, const cop_neigh *g, const cop_f
         p.tab.verify = (cfg->flags & COP_FWD_VERIFY_CSUM) ? 1u : 0u;
         p.tab.miss_nh = cfg->miss_nh;
         p.seg = seg ? 1u : 0u;
-        p.scratch = c->fwd_scratch[lane];
-        auto flush = [&]() -> int {
-            const hipError_t e = rewrite ? copk_fwd_rewrite_launch(&p, s) : copk_fwd_check_launch(&p, s);
-            p.scratch_begin += p.nchunks;   // <= max_batches * cpb * n_lists: nb <= max_batches, n <= max_batch
-            p.nl = 0;
-            p.nchunks = 0;
-            return e == hipSuccess ? 0 : set_err(c, -EIO, "%s launch: %s", what, hipGetErrorString(e));
-        };
-        for (uint32_t i = 0; i < nb; i++) {
-            const cop_batch &b = batches[i];
-            if (!b.n) continue;
-            const uint32_t chunks = (b.n + COPK_FWD_CHUNK - 1) / COPK_FWD_CHUNK;
-            for (uint32_t q = 0; q < n_lists; q++) {
-                if (p.nl == COPK_FWD_MAXL)
-                    if (int rc = flush()) return rc;
-                CopKFwdList &l = p.l[p.nl++];
-                memset(&l, 0, sizeof(l));
-                l.pkts = (const uint8_t *)b.pkts + b.data_off;
-                l.offsets = b.offsets;
-                l.results = b.results;
-                l.idx = b.fwd_idx + (size_t)q * b.n;
-                l.count = b.fwd_count + q;
-                l.n = b.n;
-                l.stride = b.stride;
-                l.chunk_begin = p.nchunks;
-                fill(l, i, q);
-                p.nchunks += chunks;
-            }
-        }
-        return flush();
+        if (int rc = side_scratch(c, cop_ctx::SIDE_FWD, lane, chunk_scratch_bytes(c, n_lists, COPK_FWD_SCRATCH_WORDS),
+                                  &p.scratch))
+            return rc;
+        return pack_lists(c, what, p, COPK_FWD_MAXL, rewrite ? copk_fwd_rewrite_launch : copk_fwd_check_launch, s, batches,
+                          nb, n_lists, [&](CopKFwdList &l, uint32_t i, uint32_t q) {
+                              l.results = batches[i].results;
+                              fill(l, i, q);
+                          });
     });
 }
 
@@ -4538,12 +4503,10 @@ int cop_fwd_check(cop_ctx *c, const cop_neigh *g, const cop_fwd_config *cfg, con
     if (nb == 0) return 0;
     uint32_t n_lists = 1;
     int seg = 0;
-    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
-    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "fwd_check: nb %u > max_batches", nb);
-    const char *why = "";
-    if (int rc = cop_fwd_check_validate(g->entries, g->n_entries, cfg, batches, desc, nb, n_lists, seg, c->cfg.max_batch,
-                                        &why))
-        return set_err(c, rc, "fwd_check: %s", why);
+    if (int rc = list_call_check(c, "fwd_check", nb, &n_lists, &seg, [&](uint32_t nl, int sg, const char **why) {
+            return cop_fwd_check_validate(g->entries, g->n_entries, cfg, batches, desc, nb, nl, sg, c->cfg.max_batch, why);
+        }))
+        return rc;
     return fwd_run(c, "fwd_check", g, cfg, batches, nb, n_lists, seg, false, [&](CopKFwdList &l, uint32_t i, uint32_t q) {
         const cop_fwd_check_desc &d = desc[i];
         const size_t at = (size_t)q * batches[i].n;
@@ -4564,12 +4527,11 @@ int cop_fwd_rewrite(cop_ctx *c, const cop_neigh *g, const cop_fwd_config *cfg, c
     if (nb == 0) return 0;
     uint32_t n_lists = 1;
     int seg = 0;
-    if (int rc = tx_layout(c, &n_lists, &seg)) return rc;
-    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "fwd_rewrite: nb %u > max_batches", nb);
-    const char *why = "";
-    if (int rc = cop_fwd_rewrite_validate(g->entries, g->n_entries, cfg, batches, tx, rw, nb, n_lists, seg,
-                                          c->cfg.max_batch, &why))
-        return set_err(c, rc, "fwd_rewrite: %s", why);
+    if (int rc = list_call_check(c, "fwd_rewrite", nb, &n_lists, &seg, [&](uint32_t nl, int sg, const char **why) {
+            return cop_fwd_rewrite_validate(g->entries, g->n_entries, cfg, batches, tx, rw, nb, nl, sg, c->cfg.max_batch,
+                                            why);
+        }))
+        return rc;
     return fwd_run(c, "fwd_rewrite", g, cfg, batches, nb, n_lists, seg, true, [&](CopKFwdList &l, uint32_t i, uint32_t q) {
         const cop_tx_burst &o = tx[i].out[q];
         l.frames = (uint8_t *)o.frames;

@@ -19,35 +19,27 @@
 //
 // Query (cop_sketch_est): one address per lane, a gather of `rows` words.
 //
-// Police: the chunk walk of cop_tx.hip, one workgroup per 256 positions of one
-// list (a segment of a segmented list), no atomics and no workgroup waiting
-// for another. cop_sketch_pol_mark looks every entry's packet up and writes the
-// chunk's keep bits (one ballot per wave), the waves' kept counts and the
-// chunk's length to context-owned scratch; cop_sketch_pol_write, on the same
-// grid, places the kept entries: a chunk's output base is the sum of the
-// earlier chunks' kept counts (dense, per vport) or the segment's own start,
-// a lane's place the kept bits below it. Chunk 0 of a list, which exists for
-// every list, sums all chunks and writes status (and a dense list's
-// out_count); a segment's chunk writes its out_count word. The estimates are
-// computed once, in the first kernel.
+// Police: the chunk grid of cop_chunk.h and its mark record.
+// cop_sketch_pol_mark looks every entry's packet up and marks the entries to
+// keep; cop_sketch_pol_write, on the same grid, places them. Chunk 0 of a list
+// writes status (and a dense list's out_count); a segment's chunk writes its
+// out_count word. The estimates are computed once, in the first kernel.
 //
 // Decay (cop_sketch_decay): a 16-byte-per-lane sweep.
 //
 // Only vector loads, stores and atomics, in plain C++ and __hip_atomic_*.
 //
-// Bounds: a column is below cols by its shift, a row below rows <= 4; a list
-// index >= n is read as n - 1; a count is clamped to what the layout holds, so
-// a kept entry's place is below the list's (segment's) capacity.
+// Bounds: a column is below cols by its shift, a row below rows <= 4; the
+// lists' are cop_chunk.h's.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cop_kernels.h"
+#include "cop_chunk.h"
 
 namespace {
 
-constexpr int BLOCK = COPK_SK_CHUNK;
+constexpr int BLOCK = CHUNK;
 constexpr uint32_t SLOTS = 512;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64x2 __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ uint32_t col_of(const CopKSketch &s, uint32_t r, uint32_t k)
@@ -96,9 +88,7 @@ __global__ __launch_bounds__(BLOCK) void cop_sketch_add(const CopKSkUpdate p)
     __shared__ unsigned long long s_key[SLOTS];   // 0: free; else 1 << 32 | key
     __shared__ uint32_t s_cnt[SLOTS];
     const int tid = threadIdx.x, lane = tid & 63;
-    uint32_t bi = 0;
-    while (bi + 1 < p.nb && blockIdx.x >= p.b[bi + 1].chunk_begin) bi++;
-    const CopKSkBatch &B = p.b[bi];
+    const CopKSkBatch &B = p.b[item_of(p.nb, blockIdx.x, [&](uint32_t i) { return p.b[i].chunk_begin; })];
     const uint32_t i = (blockIdx.x - B.chunk_begin) * BLOCK + (uint32_t)tid;
 
     bool counts = false;
@@ -170,102 +160,39 @@ __global__ __launch_bounds__(BLOCK) void cop_sketch_decay(const CopKSketch s, ui
 }
 
 // ---- police -------------------------------------------------------------------
-__device__ __forceinline__ uint32_t list_of(const CopKSkPolice &p, uint32_t wg)
-{
-    uint32_t li = 0;
-    while (li + 1 < p.nl && wg >= p.l[li + 1].chunk_begin) li++;
-    return li;
-}
-
-// entries of chunk c of a list over a batch of n packets
-__device__ __forceinline__ uint32_t chunk_count(const CopKSkList &L, uint32_t seg, uint32_t c)
-{
-    const uint32_t first = c * BLOCK;
-    if (seg) return min(L.count[c], L.n > first ? min(L.n - first, (uint32_t)BLOCK) : 0u);
-    const uint32_t total = min(L.count[0], L.n);
-    return total > first ? min(total - first, (uint32_t)BLOCK) : 0u;
-}
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// scratch of a chunk: words 0..7 the four waves' keep ballots, 8..11 their kept counts, 12 the chunk's entries
 __global__ __launch_bounds__(BLOCK) void cop_sketch_pol_mark(const CopKSkPolice p)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKSkList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t cnt = chunk_count(L, p.seg, c);
+    const CopKSkList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    const uint32_t cnt = chunk_count(L.h, p.seg, c);
     bool keep = false;
-    if ((uint32_t)tid < cnt) {
-        const uint32_t i = min(L.idx[(size_t)c * BLOCK + tid], L.n - 1u);
+    if (threadIdx.x < cnt) {
         uint32_t key;
-        keep = !packet_key(p.sk, L.pkts, L.offsets, L.stride, i, key) || est_of(p.sk, key) < L.threshold;
+        keep = !packet_key(p.sk, L.h.pkts, L.h.offsets, L.h.stride, chunk_entry(L.h, c, threadIdx.x), key) ||
+               est_of(p.sk, key) < L.threshold;
     }
-    const unsigned long long bits = __ballot(keep);
-    uint32_t *const sc = p.scratch + (size_t)(p.scratch_begin + blockIdx.x) * COPK_SK_SCRATCH_WORDS;
-    if (lane == 0) {
-        sc[2 * wave] = (uint32_t)bits;
-        sc[2 * wave + 1] = (uint32_t)(bits >> 32);
-        sc[8 + wave] = (uint32_t)__popcll(bits);
-    }
-    if (tid == 0) sc[12] = cnt;
+    mark_put(p.scratch + (size_t)(p.scratch_begin + blockIdx.x) * COPK_SK_SCRATCH_WORDS, keep, cnt);
 }
 
 __global__ __launch_bounds__(BLOCK) void cop_sketch_pol_write(const CopKSkPolice p)
 {
     __shared__ uint32_t red[4][2];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKSkList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t nchunk = (L.n + BLOCK - 1) / BLOCK;
-    const uint32_t *const sc0 = p.scratch + (size_t)(p.scratch_begin + L.chunk_begin) * COPK_SK_SCRATCH_WORDS;
-    const uint32_t *const sc = sc0 + (size_t)c * COPK_SK_SCRATCH_WORDS;
-    const uint32_t cnt = sc[12];
-    if (!cnt && c != 0) {   // past the list's end, or an empty segment
+    const uint32_t tid = threadIdx.x;
+    const CopKSkList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    MarkAt m;
+    uint32_t v[2] = {0u, 0u};   // kept and entries of the chunks before this one; chunk 0: of every chunk
+    if (!mark_get(p.scratch + (size_t)(p.scratch_begin + L.h.chunk_begin) * COPK_SK_SCRATCH_WORDS, COPK_SK_SCRATCH_WORDS,
+                  p.seg, c, (L.h.n + BLOCK - 1) / BLOCK, m, v, red, [](const uint32_t *, uint32_t (&)[2]) {})) {
         if (p.seg && tid == 0) L.out_count[c] = 0u;
         return;
     }
-
-    // kept and entries of the chunks before this one; chunk 0: of every chunk
-    uint32_t kept = 0, ents = 0;
-    const uint32_t upto = c ? c : nchunk;
-    if (c == 0 || !p.seg) {
-        for (uint32_t s = tid; s < upto; s += BLOCK) {
-            const u32x4 k = *(const u32x4 *)(sc0 + (size_t)s * COPK_SK_SCRATCH_WORDS + 8);
-            kept += k.x + k.y + k.z + k.w;
-            ents += sc0[(size_t)s * COPK_SK_SCRATCH_WORDS + 12];
-        }
-        kept = wave_sum(kept);
-        ents = wave_sum(ents);
-        if (lane == 0) {
-            red[wave][0] = kept;
-            red[wave][1] = ents;
-        }
-        __syncthreads();
-        kept = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        ents = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    }
-    const u32x4 wk = *(const u32x4 *)(sc + 8);
     if (c == 0 && tid == 0) {
-        __builtin_nontemporal_store(u32x4{kept, ents - kept, 0u, 0u}, (u32x4 *)L.status);
-        if (!p.seg) L.out_count[0] = kept;
+        __builtin_nontemporal_store(u32x4{v[0], v[1] - v[0], 0u, 0u}, (u32x4 *)L.status);
+        if (!p.seg) L.out_count[0] = v[0];
     }
-    if (p.seg && tid == 0) L.out_count[c] = wk.x + wk.y + wk.z + wk.w;
-    if ((uint32_t)tid >= cnt) return;
-
-    const unsigned long long bits = ((unsigned long long)sc[2 * wave + 1] << 32) | sc[2 * wave];
-    if (!((bits >> lane) & 1ull)) return;
-    const uint32_t before = (wave > 0 ? wk.x : 0u) + (wave > 1 ? wk.y : 0u) + (wave > 2 ? wk.z : 0u) +
-                            (uint32_t)__popcll(bits & ((1ull << lane) - 1ull));
-    const size_t base = p.seg ? (size_t)c * BLOCK : (size_t)(c ? kept : 0u);
-    L.out_idx[base + before] = L.idx[(size_t)c * BLOCK + tid];
+    if (p.seg && tid == 0) L.out_count[c] = m.kept_here;
+    if (tid < m.cnt && m.keep) L.out_idx[mark_base(p.seg, c, v[0]) + m.before] = L.h.idx[(size_t)c * BLOCK + tid];
 }
 
 }  // namespace

@@ -1,19 +1,15 @@
 // cop_tx.hip — cop_tx_sums / cop_tx_copy: forwarded frames packed into tx
 // bursts (cop_tx_gather, include/cop_gpu.h; host mirror: tx_gather.c).
 //
-// The host does not know the list lengths, so the grid is sized from n: one
-// workgroup per chunk of 256 consecutive positions of one list (a segment of
-// a segmented list; positions 256c .. of a dense or per-vport list). A chunk
-// past its list's end leaves after reading the count. No atomics, and no
-// workgroup waits for another:
-//   - a chunk's first list position is 256c (dense, per vport) or the sum of
-//     the earlier segments' counts, read and reduced inside the workgroup (at
-//     most 1,024 words for a 262,144-packet batch, from L2);
+// The kernels run on the chunk grid of cop_chunk.h: one workgroup per 256
+// consecutive positions of one list, no atomics, no workgroup waiting for
+// another. Where a chunk's frames go:
 //   - a slot batch's byte offsets are arithmetic (k * slot_bytes);
 //   - an IMIX batch's chunk starts at the sum of the earlier chunks' extents:
 //     cop_tx_sums, a pre-pass on the same grid, writes each chunk's byte sum to
-//     context-owned scratch, cop_tx_copy sums the entries before its own and
-//     scans inside the chunk.
+//     context-owned scratch, cop_tx_copy sums the entries before its own (in
+//     the reduction that finds a segmented chunk's place) and scans inside the
+//     chunk.
 //
 // status is written by exactly one chunk of every list, which finds out by
 // itself that it is the one: the chunk holding the first frame that does not
@@ -38,52 +34,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "cop_kernels.h"
+#include "cop_chunk.h"
 
 namespace {
 
-constexpr int BLOCK = COPK_TX_CHUNK;
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d, 64);
-    return v;
-}
-
-// sums of three values over the workgroup (every thread gets them)
-__device__ __forceinline__ void block_sum3(uint32_t &a, uint32_t &b, uint32_t &c, uint32_t (*red)[3], int lane,
-                                           int wave)
-{
-    a = wave_sum(a);
-    b = wave_sum(b);
-    c = wave_sum(c);
-    __syncthreads();   // red may still be read from an earlier use
-    if (lane == 0) {
-        red[wave][0] = a;
-        red[wave][1] = b;
-        red[wave][2] = c;
-    }
-    __syncthreads();
-    a = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-    b = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    c = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-}
-
-// the list and chunk of this workgroup
-__device__ __forceinline__ uint32_t list_of(const CopKTx &p, uint32_t wg)
-{
-    uint32_t li = 0;
-    while (li + 1 < p.nl && wg >= p.l[li + 1].chunk_begin) li++;
-    return li;
-}
-
-__device__ __forceinline__ uint32_t chunk_cap(uint32_t n, uint32_t c)
-{
-    const uint32_t first = c * BLOCK;
-    return n > first ? min(n - first, (uint32_t)BLOCK) : 0u;
-}
+constexpr int BLOCK = CHUNK;
 
 __device__ __forceinline__ uint32_t frame_ext(uint32_t len, uint32_t &l)
 {
@@ -95,28 +50,19 @@ __device__ __forceinline__ uint32_t frame_ext(uint32_t len, uint32_t &l)
 __global__ __launch_bounds__(BLOCK) void cop_tx_sums(const CopKTx p)
 {
     __shared__ uint32_t red[4][3];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKTxList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t n = L.n;
-    if (!n) return;
-    uint32_t cnt;
-    if (p.seg) {
-        cnt = min(L.count[c], chunk_cap(n, c));
-    } else {
-        const uint32_t total = min(L.count[0], n);
-        cnt = total > c * BLOCK ? min(total - c * BLOCK, (uint32_t)BLOCK) : 0u;
-        if (!cnt) return;
-    }
-    uint32_t ext = 0, z0 = 0, z1 = 0;
+    const int tid = threadIdx.x;
+    const CopKTxList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    if (!L.h.n) return;
+    const uint32_t cnt = chunk_count(L.h, p.seg, c);
+    if (!cnt && !p.seg) return;
+    uint32_t v[3] = {0u, 0u, 0u};
     if ((uint32_t)tid < cnt) {
-        const uint32_t i = min(L.idx[c * BLOCK + tid], n - 1u);
         uint32_t l;
-        ext = frame_ext(L.lens[i], l);
+        v[0] = frame_ext(L.lens[chunk_entry(L.h, c, tid)], l);
     }
-    block_sum3(ext, z0, z1, red, lane, wave);
-    if (tid == 0) p.sums[L.sums_begin + c] = ext;
+    block_sum(v, red);
+    if (tid == 0) p.sums[L.sums_begin + c] = v[0];
 }
 
 template <bool IMIX>
@@ -126,43 +72,25 @@ __global__ __launch_bounds__(BLOCK) void cop_tx_copy(const CopKTx p)
     __shared__ uint32_t s_src[BLOCK];       // slot: packet index; IMIX: offsets[i]
     __shared__ uint32_t s_off[BLOCK + 1];   // IMIX: byte offset inside the chunk; [cnt] = the chunk's bytes
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const uint32_t li = list_of(p, blockIdx.x);
-    const CopKTxList &L = p.l[li];
-    const uint32_t c = blockIdx.x - L.chunk_begin;
-    const uint32_t n = L.n;
-    if (!n) {   // an empty batch: one chunk, a zero status
+    const CopKTxList &L = p.l[list_of(p, blockIdx.x)];
+    const uint32_t c = blockIdx.x - L.h.chunk_begin;
+    if (!L.h.n) {   // an empty batch: one chunk, a zero status
         if (tid == 0) __builtin_nontemporal_store(u32x4{0u, 0u, 0u, 0u}, (u32x4 *)L.status);
         return;
     }
-    const uint32_t nchunk = (n + BLOCK - 1) / BLOCK;
 
     // the chunk's frames, its first list position k0, the list's length, the chunk's byte base (IMIX)
-    uint32_t cnt, k0, total, bytes0 = 0;
-    if (p.seg) {
-        uint32_t tot = 0, pre = 0, bpre = 0;
-        for (uint32_t s = tid; s < nchunk; s += BLOCK) {
-            const uint32_t v = min(L.count[s], chunk_cap(n, s));
-            tot += v;
-            if (s < c) {
-                pre += v;
-                if (IMIX) bpre += p.sums[L.sums_begin + s];
-            }
-        }
-        block_sum3(tot, pre, bpre, red, lane, wave);
-        cnt = min(L.count[c], chunk_cap(n, c));
-        k0 = pre;
-        total = tot;
-        bytes0 = bpre;
-    } else {
-        total = min(L.count[0], n);
-        k0 = c * BLOCK;
-        if (k0 >= total && c != 0) return;   // past the list's end
-        cnt = min(total - k0, (uint32_t)BLOCK);
+    const uint32_t *const sums = IMIX ? p.sums + L.sums_begin : nullptr;
+    const ChunkAt at = chunk_locate(L.h, p.seg, c, sums, red);
+    const uint32_t cnt = at.cnt, k0 = at.k0, total = at.total;
+    uint32_t bytes0 = at.extra_before;
+    if (!p.seg) {
+        if (!cnt && c != 0) return;   // past the list's end
         if (IMIX) {
-            uint32_t bpre = 0, z0 = 0, z1 = 0;
-            for (uint32_t s = tid; s < c; s += BLOCK) bpre += p.sums[L.sums_begin + s];
-            block_sum3(bpre, z0, z1, red, lane, wave);
-            bytes0 = bpre;
+            uint32_t v[3] = {0u, 0u, 0u};
+            for (uint32_t s = tid; s < c; s += BLOCK) v[0] += sums[s];
+            block_sum(v, red);
+            bytes0 = v[0];
         }
     }
 
@@ -170,10 +98,10 @@ __global__ __launch_bounds__(BLOCK) void cop_tx_copy(const CopKTx p)
     const uint32_t k = k0 + (uint32_t)tid;
     uint32_t ext = 0, len = 0, off = 0, src = 0;
     if ((uint32_t)tid < cnt) {
-        const uint32_t i = min(L.idx[c * BLOCK + tid], n - 1u);
+        const uint32_t i = chunk_entry(L.h, c, tid);
         if (IMIX) {
             ext = frame_ext(L.lens[i], len);
-            src = L.offsets[i];
+            src = L.h.offsets[i];
         } else {
             ext = len = L.copy_bytes;
             src = i;
@@ -205,8 +133,9 @@ __global__ __launch_bounds__(BLOCK) void cop_tx_copy(const CopKTx p)
     s_src[tid] = src;
     const bool fits = (uint32_t)tid < cnt && k < L.cap_frames && off64 + ext <= (unsigned long long)L.cap_bytes;
     // fits is monotone in the position: w = the frames of this chunk that are written
-    uint32_t w = fits ? 1u : 0u, z0 = 0, z1 = 0;
-    block_sum3(w, z0, z1, red, lane, wave);   // (its barriers also publish s_src / s_off)
+    uint32_t fit[3] = {fits ? 1u : 0u, 0u, 0u};
+    block_sum(fit, red);   // (its barriers also publish s_src / s_off)
+    const uint32_t w = fit[0];
     if (fits) {
         if (L.off) L.off[k] = off;
         if (L.len) L.len[k] = len;
@@ -227,7 +156,7 @@ __global__ __launch_bounds__(BLOCK) void cop_tx_copy(const CopKTx p)
     if (!w) return;
 
     // the copy: 16 bytes per lane, four pieces in flight
-    const uint8_t *const pk = L.pkts;
+    const uint8_t *const pk = L.h.pkts;
     uint8_t *const out = L.frames;
     if (IMIX) {
         const uint32_t pieces = s_off[w] >> 4;
@@ -258,7 +187,7 @@ __global__ __launch_bounds__(BLOCK) void cop_tx_copy(const CopKTx p)
         const uint32_t pieces = w * P;
         const bool pow2 = (P & (P - 1u)) == 0;
         const uint32_t sh = 31u - (uint32_t)__clz(P);
-        const unsigned long long stride = L.stride, slot = L.slot_bytes;
+        const unsigned long long stride = L.h.stride, slot = L.slot_bytes;
         uint8_t *const dst0 = out + (unsigned long long)k0 * slot;
         for (uint32_t q0 = tid; q0 < pieces; q0 += 4 * BLOCK) {
             u32x4 v[4];

@@ -15,45 +15,6 @@
 
 #include "cop_internal.h"
 
-typedef struct {
-    uintptr_t a, b;   /* [a, b) */
-    int w;            /* the call writes it */
-} span;
-
-static int span_cmp(const void *x, const void *y)
-{
-    const uintptr_t a = ((const span *)x)->a, b = ((const span *)y)->a;
-    return a < b ? -1 : a > b;
-}
-
-static void put(span *v, uint32_t *k, const void *p, uint64_t bytes, int w)
-{
-    if (!p || !bytes) return;
-    v[*k].a = (uintptr_t)p;
-    v[*k].b = (uintptr_t)p + bytes;
-    v[*k].w = w;
-    (*k)++;
-}
-
-/* 1 iff a written extent meets any other extent (sorted by start: an extent
- * meets an earlier one iff it starts below the largest end so far) */
-static int any_overlap(span *v, uint32_t k)
-{
-    qsort(v, k, sizeof(span), span_cmp);
-    uintptr_t end_all = 0, end_w = 0;
-    for (uint32_t i = 0; i < k; i++) {
-        if (v[i].a < (v[i].w ? end_all : end_w)) return 1;
-        if (v[i].b > end_all) end_all = v[i].b;
-        if (v[i].w && v[i].b > end_w) end_w = v[i].b;
-    }
-    return 0;
-}
-
-static uint32_t count_words(uint32_t n, uint32_t n_lists, int seg)
-{
-    return seg ? (n + COP_SEG_PKTS - 1) / COP_SEG_PKTS : n_lists;
-}
-
 static int common_check(const void *entries, uint32_t n_entries, const cop_fwd_config *cfg, uint32_t n_lists, int seg,
                         const char **why)
 {
@@ -71,15 +32,11 @@ static int common_check(const void *entries, uint32_t n_entries, const cop_fwd_c
 /* what both calls read of a batch */
 static int batch_check(const cop_batch *b, uint32_t max_batch, const char **why)
 {
-    const int imix = b->offsets != NULL;
     *why = "n > max_batch or n > 1 << 28";
     if ((max_batch && b->n > max_batch) || b->n > (1u << 28)) return -EINVAL;
-    *why = "a batch with packets needs pkts, fwd_idx and fwd_count";
-    if (b->n && (!b->pkts || !b->fwd_idx || !b->fwd_count)) return -EINVAL;
-    *why = "packet starts must be 16-byte aligned (pkts, data_off, stride)";
-    if (((uintptr_t)b->pkts & 15) || (b->data_off & 15) || (!imix && (b->stride & 15))) return -EINVAL;
+    if (cop_batch_lists_check(b, why)) return -EINVAL;
     *why = "a slot batch's stride must be at least 48 (header records are not taken)";
-    if (!imix && b->n && b->stride < 48) return -EINVAL;
+    if (!b->offsets && b->n && b->stride < 48) return -EINVAL;
     *why = "offsets / fwd_idx / fwd_count must be 4-byte aligned, results 8-byte aligned";
     if ((((uintptr_t)b->offsets | (uintptr_t)b->fwd_idx | (uintptr_t)b->fwd_count) & 3) || ((uintptr_t)b->results & 7))
         return -EINVAL;
@@ -110,30 +67,25 @@ int cop_fwd_check_validate(const void *entries, uint32_t n_entries, const cop_fw
               (uintptr_t)d->exc_count) & 3) || ((uintptr_t)d->status & 15))
             return -EINVAL;
     }
-    span *v = (span *)malloc(((size_t)nb * 11 + 1) * sizeof(span));
+    cop_extent *v = (cop_extent *)malloc(((size_t)nb * 11 + 1) * sizeof(cop_extent));
     *why = "out of memory";
     if (!v) return -ENOMEM;
     uint32_t k = 0;
-    put(v, &k, entries, 16ull * n_entries, 0);
+    cop_extent_put(v, &k, entries, 16ull * n_entries, 0);
     for (uint32_t i = 0; i < nb; i++) {
         const cop_batch *b = &batches[i];
         const cop_fwd_check_desc *d = &desc[i];
-        const uint64_t n = b->n, idx_bytes = n * 4 * (seg ? 1u : n_lists), cnt_bytes = 4ull * count_words(b->n, n_lists, seg);
+        const uint64_t n = b->n, idx_bytes = n * 4 * (seg ? 1u : n_lists),
+                       cnt_bytes = 4ull * cop_tx_fwd_count_words(b->n, n_lists, seg);
         if (!n) continue;
-        /* an IMIX slab's size is not known here: its first byte stands for it */
-        put(v, &k, b->pkts, b->offsets ? 16 : n * b->stride, 0);
-        put(v, &k, b->offsets, n * 4, 0);
-        put(v, &k, d->lens, n * 4, 0);
-        put(v, &k, b->results, n * 8, 0);
-        put(v, &k, b->fwd_idx, idx_bytes, 0);
-        put(v, &k, b->fwd_count, cnt_bytes, 0);
-        put(v, &k, d->out_idx, idx_bytes, 1);
-        put(v, &k, d->out_count, cnt_bytes, 1);
-        put(v, &k, d->exc_idx, idx_bytes, 1);
-        put(v, &k, d->exc_count, cnt_bytes, 1);
-        put(v, &k, d->status, 16ull * n_lists, 1);
+        cop_extent_put_batch(v, &k, b, d->lens, n_lists, seg);
+        cop_extent_put(v, &k, d->out_idx, idx_bytes, 1);
+        cop_extent_put(v, &k, d->out_count, cnt_bytes, 1);
+        cop_extent_put(v, &k, d->exc_idx, idx_bytes, 1);
+        cop_extent_put(v, &k, d->exc_count, cnt_bytes, 1);
+        cop_extent_put(v, &k, d->status, 16ull * n_lists, 1);
     }
-    const int bad = any_overlap(v, k);
+    const int bad = cop_extents_clash(v, k, 0);
     free(v);
     *why = "an output extent overlaps another extent of the call or the table";
     if (bad) return -EINVAL;
@@ -165,29 +117,29 @@ int cop_fwd_rewrite_validate(const void *entries, uint32_t n_entries, const cop_
                 return -EINVAL;
         }
     }
-    span *v = (span *)malloc(((size_t)nb * (3 + 6 * COP_MAX_DEMUX_PORTS) + 1) * sizeof(span));
+    cop_extent *v = (cop_extent *)malloc(((size_t)nb * (3 + 6 * COP_MAX_DEMUX_PORTS) + 1) * sizeof(cop_extent));
     *why = "out of memory";
     if (!v) return -ENOMEM;
     uint32_t k = 0;
-    put(v, &k, entries, 16ull * n_entries, 0);
+    cop_extent_put(v, &k, entries, 16ull * n_entries, 0);
     for (uint32_t i = 0; i < nb; i++) {
         const cop_batch *b = &batches[i];
         const uint64_t n = b->n;
         if (!n) continue;
-        put(v, &k, b->results, n * 8, 0);
-        put(v, &k, b->fwd_idx, n * 4 * (seg ? 1u : n_lists), 0);
-        put(v, &k, b->fwd_count, 4ull * count_words(b->n, n_lists, seg), 0);
+        cop_extent_put(v, &k, b->results, n * 8, 0);
+        cop_extent_put(v, &k, b->fwd_idx, n * 4 * (seg ? 1u : n_lists), 0);
+        cop_extent_put(v, &k, b->fwd_count, 4ull * cop_tx_fwd_count_words(b->n, n_lists, seg), 0);
         for (uint32_t q = 0; q < n_lists; q++) {
             const cop_tx_burst *o = &tx[i].out[q];
-            put(v, &k, o->frames, o->cap_bytes, 1);
-            put(v, &k, o->off, 4ull * o->cap_frames, 0);
-            put(v, &k, o->len, 4ull * o->cap_frames, 0);
-            put(v, &k, o->status, 16, 0);
-            put(v, &k, rw[i].port[q], 4ull * o->cap_frames, 1);
-            put(v, &k, rw[i].status[q], 16, 1);
+            cop_extent_put(v, &k, o->frames, o->cap_bytes, 1);
+            cop_extent_put(v, &k, o->off, 4ull * o->cap_frames, 0);
+            cop_extent_put(v, &k, o->len, 4ull * o->cap_frames, 0);
+            cop_extent_put(v, &k, o->status, 16, 0);
+            cop_extent_put(v, &k, rw[i].port[q], 4ull * o->cap_frames, 1);
+            cop_extent_put(v, &k, rw[i].status[q], 16, 1);
         }
     }
-    const int bad = any_overlap(v, k);
+    const int bad = cop_extents_clash(v, k, 0);
     free(v);
     *why = "an output extent overlaps another extent of the call or the table";
     if (bad) return -EINVAL;

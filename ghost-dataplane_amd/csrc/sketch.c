@@ -14,21 +14,6 @@
 
 #include "cop_internal.h"
 
-typedef struct {
-    uintptr_t a, b;   /* [a, b) */
-} span;
-
-static span mk(const void *p, uint64_t bytes)
-{
-    span s = {(uintptr_t)p, (uintptr_t)p + (p ? bytes : 0)};
-    return s;
-}
-
-static int meets(span x, span y)
-{
-    return x.a < x.b && y.a < y.b && x.a < y.b && y.a < x.b;
-}
-
 static uint64_t sm64(uint64_t *s)
 {
     uint64_t z = (*s += 0x9E3779B97F4A7C15ull);
@@ -70,15 +55,14 @@ int cop_sketch_params(const cop_sketch_config *cfg, uint32_t a[4], uint32_t b[4]
 /* what a sketch call reads of a batch's packets: the checks update and police share */
 static int batch_packets_check(const cop_batch *b, uint32_t max_batch, const char **why)
 {
-    const int imix = b->offsets != NULL;
     *why = "n > max_batch";
     if (max_batch && b->n > max_batch) return -EINVAL;
     *why = "a batch with packets needs pkts";
     if (b->n && !b->pkts) return -EINVAL;
     *why = "packet starts must be 16-byte aligned (pkts, data_off, stride; 12-byte records are not taken)";
-    if (((uintptr_t)b->pkts & 15) || (b->data_off & 15) || (!imix && (b->stride & 15))) return -EINVAL;
+    if (cop_batch_misaligned(b)) return -EINVAL;
     *why = "stride must be COP_HDR16_STRIDE (records) or at least 48 (frames)";
-    if (!imix && b->n && b->stride != COP_HDR16_STRIDE && b->stride < 48) return -EINVAL;
+    if (!b->offsets && b->n && b->stride != COP_HDR16_STRIDE && b->stride < 48) return -EINVAL;
     *why = "offsets must be 4-byte aligned";
     if ((uintptr_t)b->offsets & 3) return -EINVAL;
     return 0;
@@ -114,16 +98,14 @@ int cop_sketch_query_validate(const cop_sketch_config *cfg, const void *counters
     *why = "ips must be 4-byte aligned, out 8-byte aligned";
     if (((uintptr_t)ips & 3) || ((uintptr_t)out & 7)) return -EINVAL;
     *why = "out overlaps ips or the counters";
-    const span o = mk(out, 8ull * n);
-    if (meets(o, mk(ips, 4ull * n)) || meets(o, mk(counters, ((uint64_t)cfg->rows << cfg->log2_cols) * 8)))
-        return -EINVAL;
+    cop_extent v[3];
+    uint32_t k = 0;
+    cop_extent_put(v, &k, out, 8ull * n, 1);
+    cop_extent_put(v, &k, ips, 4ull * n, 0);
+    cop_extent_put(v, &k, counters, ((uint64_t)cfg->rows << cfg->log2_cols) * 8, 0);
+    if (cop_extents_clash(v, k, 0)) return -EINVAL;
     *why = "";
     return 0;
-}
-
-static uint32_t count_words(uint32_t n, uint32_t n_lists, int seg)
-{
-    return seg ? (n + COP_SEG_PKTS - 1) / COP_SEG_PKTS : n_lists;
 }
 
 int cop_sketch_police_validate(const cop_sketch_config *cfg, const void *counters, const cop_batch *batches,
@@ -149,29 +131,23 @@ int cop_sketch_police_validate(const cop_sketch_config *cfg, const void *counter
             return -EINVAL;
     }
     /* no output extent over anything the call reads (cop_tx_validate's rule) or over the counters */
-    *why = "an output extent overlaps a batch's packets, offsets, records or lists, or the sketch's counters";
-    const span ctr = mk(counters, ((uint64_t)cfg->rows << cfg->log2_cols) * 8);
+    cop_extent *v = (cop_extent *)malloc(((size_t)nb * 8 + 1) * sizeof(cop_extent));
+    *why = "out of memory";
+    if (!v) return -ENOMEM;
+    uint32_t k = 0;
+    cop_extent_put(v, &k, counters, ((uint64_t)cfg->rows << cfg->log2_cols) * 8, 0);
     for (uint32_t i = 0; i < nb; i++) {
         const uint64_t n = batches[i].n;
         if (!n) continue;
-        const span outs[3] = {mk(pol[i].out_idx, n * 4 * (seg ? 1u : n_lists)),
-                              mk(pol[i].out_count, 4ull * count_words(batches[i].n, n_lists, seg)),
-                              mk(pol[i].status, 16ull * n_lists)};
-        for (int x = 0; x < 3; x++) {
-            if (meets(outs[x], ctr)) return -EINVAL;
-            for (uint32_t j = 0; j < nb; j++) {
-                const cop_batch *b = &batches[j];
-                const uint64_t m = b->n;
-                if (!m) continue;
-                /* an IMIX slab's size is not known here: its first byte stands for it */
-                if (meets(outs[x], mk(b->pkts, b->offsets ? 16 : m * b->stride)) ||
-                    meets(outs[x], mk(b->offsets, m * 4)) || meets(outs[x], mk(b->results, m * 8)) ||
-                    meets(outs[x], mk(b->fwd_idx, m * 4 * (seg ? 1u : n_lists))) ||
-                    meets(outs[x], mk(b->fwd_count, 4ull * count_words(b->n, n_lists, seg))))
-                    return -EINVAL;
-            }
-        }
+        cop_extent_put_batch(v, &k, &batches[i], NULL, n_lists, seg);
+        cop_extent_put(v, &k, pol[i].out_idx, n * 4 * (seg ? 1u : n_lists), 1);
+        cop_extent_put(v, &k, pol[i].out_count, 4ull * cop_tx_fwd_count_words(batches[i].n, n_lists, seg), 1);
+        cop_extent_put(v, &k, pol[i].status, 16ull * n_lists, 1);
     }
+    const int bad = cop_extents_clash(v, k, 1);
+    free(v);
+    *why = "an output extent overlaps a batch's packets, offsets, records or lists, or the sketch's counters";
+    if (bad) return -EINVAL;
     *why = "";
     return 0;
 }

@@ -15,43 +15,6 @@
 
 #include "cop_internal.h"
 
-typedef struct {
-    uintptr_t a, b;   /* [a, b) */
-} span;
-
-static int span_cmp(const void *x, const void *y)
-{
-    const uintptr_t a = ((const span *)x)->a, b = ((const span *)y)->a;
-    return a < b ? -1 : a > b;
-}
-
-static span mk(const void *p, uint64_t bytes)
-{
-    span s = {(uintptr_t)p, (uintptr_t)p + (p ? bytes : 0)};
-    return s;
-}
-
-uint32_t cop_tx_fwd_count_words(uint32_t n, uint32_t n_lists, int seg)
-{
-    return seg ? (n + COP_SEG_PKTS - 1) / COP_SEG_PKTS : n_lists;
-}
-
-/* what the gather reads of batch b: at most 6 extents */
-static int inputs_of(const cop_batch *b, const cop_tx_desc *t, uint32_t n_lists, int seg, span *out)
-{
-    int k = 0;
-    const uint64_t n = b->n;
-    if (!n) return 0;
-    /* an IMIX slab's size is not known here: its first byte stands for it */
-    out[k++] = mk(b->pkts, b->offsets ? 16 : n * b->stride);
-    out[k++] = mk(b->offsets, n * 4);
-    out[k++] = mk(t->lens, n * 4);
-    out[k++] = mk(b->results, n * 8);
-    out[k++] = mk(b->fwd_idx, n * 4 * (seg ? 1u : n_lists));
-    out[k++] = mk(b->fwd_count, 4ull * cop_tx_fwd_count_words(b->n, n_lists, seg));
-    return k;
-}
-
 int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb, uint32_t n_lists, int seg,
                     uint32_t max_batch, const char **why)
 {
@@ -69,10 +32,7 @@ int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb
         if (max_batch && b->n > max_batch) return -EINVAL;
         *why = "n * COP_TX_MAX_FRAME >= 2^32";
         if ((uint64_t)b->n * COP_TX_MAX_FRAME >= (1ull << 32)) return -EINVAL;
-        *why = "a batch with packets needs pkts, fwd_idx and fwd_count";
-        if (b->n && (!b->pkts || !b->fwd_idx || !b->fwd_count)) return -EINVAL;
-        *why = "packet starts must be 16-byte aligned (pkts, data_off, stride)";
-        if (((uintptr_t)b->pkts & 15) || (b->data_off & 15) || (!imix && (b->stride & 15))) return -EINVAL;
+        if (cop_batch_lists_check(b, why)) return -EINVAL;
         *why = "fwd_idx / fwd_count / offsets / lens must be 4-byte aligned";
         if (((uintptr_t)b->fwd_idx | (uintptr_t)b->fwd_count | (uintptr_t)b->offsets | (uintptr_t)t->lens) & 3)
             return -EINVAL;
@@ -97,47 +57,27 @@ int cop_tx_validate(const cop_batch *batches, const cop_tx_desc *tx, uint32_t nb
             if (o->cap_bytes >= (1ull << 32)) return -EINVAL;
         }
     }
-    /* no output extent over anything the call reads */
-    /* (the inputs sorted by start, with the running maximum of their ends: an
-     * output [a, b) meets one iff, among the inputs that start below b, the
-     * largest end is above a; microseconds for 32 batches, where all pairs
-     * took tens) */
-    span stack_in[6 * 32], *in = stack_in;
-    if (nb > 32 && !(in = (span *)malloc((size_t)nb * 6 * sizeof(span)))) {
-        *why = "out of memory";
-        return -ENOMEM;
-    }
-    uint32_t ni = 0;
-    for (uint32_t j = 0; j < nb; j++) {
-        span s[6];
-        const int k = inputs_of(&batches[j], &tx[j], n_lists, seg, s);
-        for (int y = 0; y < k; y++)
-            if (s[y].a < s[y].b) in[ni++] = s[y];
-    }
-    qsort(in, ni, sizeof(span), span_cmp);
-    for (uint32_t y = 1; y < ni; y++)
-        if (in[y].b < in[y - 1].b) in[y].b = in[y - 1].b;
-    int rc = 0;
-    *why = "an output extent overlaps a batch's packets, offsets, lens, records or lists";
-    for (uint32_t i = 0; i < nb && !rc; i++)
-        for (uint32_t q = 0; q < n_lists && !rc; q++) {
+    /* no output extent over anything the call reads; outputs may meet each other */
+    cop_extent *v = (cop_extent *)malloc(((size_t)nb * (6 + 4 * n_lists) + 1) * sizeof(cop_extent));
+    *why = "out of memory";
+    if (!v) return -ENOMEM;
+    uint32_t k = 0;
+    for (uint32_t i = 0; i < nb; i++) {
+        if (batches[i].n) cop_extent_put_batch(v, &k, &batches[i], tx[i].lens, n_lists, seg);
+        for (uint32_t q = 0; q < n_lists; q++) {
             const cop_tx_burst *o = &tx[i].out[q];
-            const span outs[4] = {mk(o->frames, o->cap_bytes), mk(o->off, 4ull * o->cap_frames),
-                                  mk(o->len, 4ull * o->cap_frames), mk(o->status, 16)};
-            for (int x = 0; x < 4 && !rc; x++) {
-                if (outs[x].a >= outs[x].b) continue;
-                uint32_t lo = 0, hi = ni;   /* the inputs that start below the output's end */
-                while (lo < hi) {
-                    const uint32_t mid = (lo + hi) / 2;
-                    if (in[mid].a < outs[x].b) lo = mid + 1;
-                    else hi = mid;
-                }
-                if (lo && in[lo - 1].b > outs[x].a) rc = -EINVAL;
-            }
+            cop_extent_put(v, &k, o->frames, o->cap_bytes, 1);
+            cop_extent_put(v, &k, o->off, 4ull * o->cap_frames, 1);
+            cop_extent_put(v, &k, o->len, 4ull * o->cap_frames, 1);
+            cop_extent_put(v, &k, o->status, 16, 1);
         }
-    if (in != stack_in) free(in);
-    if (!rc) *why = "";
-    return rc;
+    }
+    const int bad = cop_extents_clash(v, k, 1);
+    free(v);
+    *why = "an output extent overlaps a batch's packets, offsets, lens, records or lists";
+    if (bad) return -EINVAL;
+    *why = "";
+    return 0;
 }
 
 /* one list: positions [0, count) cut into chunks by chunk_of (dense lists:

@@ -298,7 +298,7 @@ def test_fwd_under_sanitizers(tmp_path):
     cc = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                          "-I", os.path.join(ROOT, "include"), "-I", csrc,
                          os.path.join(ROOT, "tests", "c", "fwd_check.c"), os.path.join(csrc, "fwd.c"),
-                         os.path.join(csrc, "tx_gather.c"), "-o", str(exe)], capture_output=True, text=True)
+                         os.path.join(csrc, "tx_gather.c"), os.path.join(csrc, "extents.c"), "-o", str(exe)], capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
     assert run.returncode == 0, run.stdout[-2000:] + run.stderr[-4000:]

@@ -321,7 +321,7 @@ def test_sketch_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "ghost-dataplane_amd", "csrc")
     cc = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                          "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                         os.path.join(ROOT, "tests", "c", "sketch_check.c"), os.path.join(csrc, "sketch.c"),
+                         os.path.join(ROOT, "tests", "c", "sketch_check.c"), os.path.join(csrc, "sketch.c"), os.path.join(csrc, "extents.c"),
                          "-o", str(exe)], capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)

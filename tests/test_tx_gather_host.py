@@ -172,7 +172,7 @@ def test_tx_gather_under_sanitizers(tmp_path):
     csrc = os.path.join(ROOT, "ghost-dataplane_amd", "csrc")
     cc = subprocess.run(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                          "-I", os.path.join(ROOT, "include"), "-I", csrc,
-                         os.path.join(ROOT, "tests", "c", "tx_gather_check.c"), os.path.join(csrc, "tx_gather.c"),
+                         os.path.join(ROOT, "tests", "c", "tx_gather_check.c"), os.path.join(csrc, "tx_gather.c"), os.path.join(csrc, "extents.c"),
                          "-o", str(exe)], capture_output=True, text=True)
     assert cc.returncode == 0, cc.stderr
     run = subprocess.run([str(exe)], capture_output=True, text=True)
