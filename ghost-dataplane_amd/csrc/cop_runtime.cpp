@@ -407,6 +407,9 @@ struct cop_ctx {
     uint64_t hp[6] = {0, 0, 0, 0, 0, 0};
 };
 
+// one out-of-line copy for the retiring sites, so the library's dynamic symbols do not follow the inliner
+template void std::vector<cop_ctx::Retired>::push_back(cop_ctx::Retired &&);
+
 static inline uint64_t hp_ns()
 {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(
@@ -936,6 +939,17 @@ static int upload_bkt(cop_ctx *c, DevLpm &t, const uint32_t *s, const uint32_t *
     return 0;
 }
 
+// A live image's tbl8 groups are plain, with spare ones for later updates: at
+// most twice the table's number_tbl8s (only a rule deeper than 24 puts a
+// boundary inside a /24, and within one update a /24 may take a group before
+// another gives its own back). The caller floors it (upload_lpm at n_ext,
+// which is 0 for an empty table built with number_tbl8s = 0; cop_replace_* at
+// one group).
+static uint64_t live_spare_cap(const cop_lpm_table *tab, uint32_t n_ext)
+{
+    return std::min<uint64_t>(2 * (uint64_t)tab->cfg.number_tbl8s, (uint64_t)n_ext + std::max(256u, n_ext / 2));
+}
+
 static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want_ivt, int form, bool want_trie = false,
                       bool want_bkt = false)
 {
@@ -972,15 +986,9 @@ static int upload_lpm(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, bool want
     if (trc) return trc;
     // DIR-24-8 image (always: FORCE_DIR24 and the large-table path)
     const uint32_t n_ext = cop_lpm_form_n_ext(tab, form);
-    // a live image's groups are plain, with spare ones for later updates: at
-    // most twice the table's number_tbl8s (only a rule deeper than 24 puts a
-    // boundary inside a /24, and within one update a /24 may take a group
-    // before another gives its own back); when they run out the update
-    // uploads afresh
+    // a live image has spare groups; when they run out the update uploads afresh
     uint32_t grp_cap = n_ext ? n_ext : 1;
-    if (live)
-        grp_cap = (uint32_t)std::max<uint64_t>(
-            n_ext, std::min<uint64_t>(2 * (uint64_t)tab->cfg.number_tbl8s, (uint64_t)n_ext + std::max(256u, n_ext / 2)));
+    if (live) grp_cap = (uint32_t)std::max<uint64_t>(n_ext, live_spare_cap(tab, n_ext));
     std::vector<uint32_t> h24((size_t)1 << 24);
     std::vector<uint32_t> h8((size_t)(grp_cap ? grp_cap : 1) * 256);
     cop_lpm_form_fill_dir24(tab, form, h24.data(), h8.data());
@@ -1112,7 +1120,6 @@ static void harvest_one(cop_ctx *c, Lane &L)
 }
 
 static int submit_on(cop_ctx *c, Lane &L, const cop_batch *batches, uint32_t nb, bool demux, uint32_t stages);
-static int pick_mode(const cop_ctx *c, const DevLpm &t, bool enabled, bool force_dir);
 
 int cop_submit(cop_ctx *c, const cop_batch *batches, uint32_t nb)
 {
@@ -1156,6 +1163,39 @@ static Plan plan_launch(const cop_ctx *c, uint64_t total, bool imix, uint32_t mi
                 : hdr16 ? COPK_LAY_HDR16
                 : (wide && c->coalesced) ? COPK_LAY_COALESCED
                                          : COPK_LAY_SLOTS};
+}
+
+// The two stages' table fields of a launch's parameters, as the stages are now, for a launch in table
+// modes (fw_mode, lpm_mode): the interval geometry only in the LDS interval mode. fill_launch sets them
+// for a new launch, live_run again in a paused poll-mode kernel's stored parameters.
+static void set_tables(const cop_ctx *c, CopKParams &p, int fw_mode, int lpm_mode)
+{
+    p.fw_m = fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
+    p.fw_ib = c->fw.ib;
+    p.fw_lv = c->fw.lv;
+    p.fw_iw = fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
+    p.fw_starts = c->fw.starts;
+    p.fw_vals = c->fw.vals;
+    p.fw_tbl24 = c->fw.tbl24;
+    p.fw_tbl8 = c->fw.tbl8;
+    p.fw_tbl8_packed = c->fw.tbl8_packed ? 1u : 0u;
+    p.lpm_m = lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
+    p.lpm_ib = c->lpm.ib;
+    p.lpm_lv = c->lpm.lv;
+    p.lpm_iw = lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
+    p.lpm_starts = c->lpm.starts;
+    p.lpm_vals = c->lpm.vals;
+    p.lpm_tbl24 = c->lpm.tbl24;
+    p.lpm_tbl8 = c->lpm.tbl8;
+    p.lpm_tbl8_packed = c->lpm.tbl8_packed ? 1u : 0u;
+    p.probe_nt = c->probe_nt ? 1u : 0u;
+    p.lpm_tl0 = c->lpm.tl0;
+    p.lpm_tnodes = c->lpm.tnodes;
+    p.lpm_tleaves = c->lpm.tleaves;
+    p.lpm_bidx = c->lpm.bidx;
+    p.lpm_bpairs = c->lpm.bpairs;
+    p.fw_bidx = c->fw.bidx;
+    p.fw_bpairs = c->fw.bpairs;
 }
 
 // The table / counter / option part of a launch's parameters: table modes
@@ -1207,32 +1247,7 @@ static int fill_launch(cop_ctx *c, CopKParams &p, int ppt, int *fw_mode_out, int
                            "(cop_set_route_lpm)");
         lpm_mode = COPK_TBL_DIR;
     }
-    p.fw_m = fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
-    p.fw_ib = c->fw.ib;
-    p.fw_lv = c->fw.lv;
-    p.fw_iw = fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
-    p.fw_starts = c->fw.starts;
-    p.fw_vals = c->fw.vals;
-    p.fw_tbl24 = c->fw.tbl24;
-    p.fw_tbl8 = c->fw.tbl8;
-    p.fw_tbl8_packed = c->fw.tbl8_packed ? 1u : 0u;
-    p.lpm_m = lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
-    p.lpm_ib = c->lpm.ib;
-    p.lpm_lv = c->lpm.lv;
-    p.lpm_iw = lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
-    p.lpm_starts = c->lpm.starts;
-    p.lpm_vals = c->lpm.vals;
-    p.lpm_tbl24 = c->lpm.tbl24;
-    p.lpm_tbl8 = c->lpm.tbl8;
-    p.lpm_tbl8_packed = c->lpm.tbl8_packed ? 1u : 0u;
-    p.probe_nt = c->probe_nt ? 1u : 0u;
-    p.lpm_tl0 = c->lpm.tl0;
-    p.lpm_tnodes = c->lpm.tnodes;
-    p.lpm_tleaves = c->lpm.tleaves;
-    p.lpm_bidx = c->lpm.bidx;
-    p.lpm_bpairs = c->lpm.bpairs;
-    p.fw_bidx = c->fw.bidx;
-    p.fw_bpairs = c->fw.bpairs;
+    set_tables(c, p, fw_mode, lpm_mode);
     uint32_t off = 256 + c->rt_nleaf * 128;
     p.lds_fw_off = off;
     off += 2 * p.fw_m + p.fw_iw;
@@ -1892,9 +1907,47 @@ int cop_process_host_stream(cop_ctx *c, const void *const *pkt_data, uint64_t n,
     return 0;
 }
 
-static int pmd_hits_flush(cop_ctx *c);
+// the poll-mode kernel's side of what follows (defined with the kernel's host code below)
 static int pmd_pause(cop_ctx *c);
 static int pmd_resume(cop_ctx *c);
+static int pmd_hits_flush(cop_ctx *c);
+static int pmd_hits_sync(cop_pmd *m, uint64_t upto);
+static uint64_t pmd_refresh(cop_pmd *m, uint32_t r);
+
+// op() with the GPU free of the context's poll-mode kernel, if one serves it: pmd_pause, op(),
+// pmd_resume, whatever op() returned (a pause that fails runs neither); the first error. The one place
+// that pairs the two: the pause takes the relaunch lock and only the resume gives it back.
+static int paused(cop_ctx *c, const std::function<int()> &op)
+{
+    if (int rc = pmd_pause(c)) return rc;
+    const int rc = op();
+    const int rrc = pmd_resume(c);
+    return rc ? rc : rrc;
+}
+
+// paused(), for an op() that queues on c->stream (0, or an error it has set): the stream is drained
+// before the resume; `fail` is the error of a drain that failed.
+static int paused_op(cop_ctx *c, const char *fail, const std::function<int()> &op)
+{
+    return paused(c, [&]() -> int {
+        int rc = op();
+        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s", fail);
+        return rc;
+    });
+}
+
+// Room for `need` u64 words in a device buffer of `have`: the old one is freed first (hipFree
+// synchronises the whole device), then the new one allocated.
+static int grow_dev(cop_ctx *c, unsigned long long *&ptr, size_t &have, size_t need)
+{
+    if (have >= need) return 0;
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    have = 0;
+    HIPCHK(c, hipMalloc(&ptr, need * 8));
+    have = need;
+    return 0;
+}
 
 // The telemetry scratch: every counter word (shards, port shards, rules),
 // so a snapshot never reallocates it (hipFree synchronises the whole
@@ -1903,15 +1956,7 @@ static int tele_scratch(cop_ctx *c)
 {
     HIPCHK(c, hipSetDevice(c->device));
     if (!c->tele_stream) HIPCHK(c, hipStreamCreateWithFlags(&c->tele_stream, hipStreamNonBlocking));
-    const size_t n = RULE_OFF + c->n_rule_ctr;
-    if (c->tele_words < n) {
-        if (c->tele_dev) (void)hipFree(c->tele_dev);
-        c->tele_dev = nullptr;
-        c->tele_words = 0;
-        HIPCHK(c, hipMalloc(&c->tele_dev, n * 8));
-        c->tele_words = n;
-    }
-    return 0;
+    return grow_dev(c, c->tele_dev, c->tele_words, RULE_OFF + c->n_rule_ctr);
 }
 
 // Counter words [off, off + n) of the counter block into host memory `out`,
@@ -1919,24 +1964,23 @@ static int tele_scratch(cop_ctx *c)
 // the telemetry stream: an increment lands before the exchange (this read)
 // or after it (the next), none is lost or counted twice. Beside one-shot
 // launches it does not wait for them. A poll-mode kernel is paused for it
-// (pmd_pause: a kernel of another stream is not guaranteed a place beside
+// (paused: a kernel of another stream is not guaranteed a place beside
 // it) and relaunched after.
 static int exchange_words(cop_ctx *c, size_t off, size_t n, uint64_t *out, int reset)
 {
     if (int rc = tele_scratch(c)) return rc;
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = 0;
-    for (size_t done = 0; done < n && !rc;) {
-        const uint32_t k = (uint32_t)std::min<size_t>(n - done, (size_t)1 << 30);
-        hipError_t e = copk_snapshot(c->counters + off + done, k, c->tele_dev + done, reset ? 1 : 0, c->tele_stream);
-        if (e != hipSuccess) rc = set_err(c, -EIO, "snapshot: %s", hipGetErrorString(e));
-        done += k;
-    }
-    if (!rc && hipMemcpyAsync(out, c->tele_dev, n * 8, hipMemcpyDeviceToHost, c->tele_stream) != hipSuccess)
-        rc = set_err(c, -EIO, "snapshot copy");
-    if (!rc && hipStreamSynchronize(c->tele_stream) != hipSuccess) rc = set_err(c, -EIO, "snapshot sync");
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
+    return paused(c, [&]() -> int {
+        for (size_t done = 0; done < n;) {
+            const uint32_t k = (uint32_t)std::min<size_t>(n - done, (size_t)1 << 30);
+            hipError_t e = copk_snapshot(c->counters + off + done, k, c->tele_dev + done, reset ? 1 : 0, c->tele_stream);
+            if (e != hipSuccess) return set_err(c, -EIO, "snapshot: %s", hipGetErrorString(e));
+            done += k;
+        }
+        if (hipMemcpyAsync(out, c->tele_dev, n * 8, hipMemcpyDeviceToHost, c->tele_stream) != hipSuccess)
+            return set_err(c, -EIO, "snapshot copy");
+        if (hipStreamSynchronize(c->tele_stream) != hipSuccess) return set_err(c, -EIO, "snapshot sync");
+        return 0;
+    });
 }
 
 int cop_counters_read(cop_ctx *c, cop_counters *out, int reset)
@@ -2098,23 +2142,6 @@ int cop_coll_unique_id(uint8_t id[COP_COLL_ID_BYTES])
     return 0;
 }
 
-static int coll_init_free(cop_ctx *c, const uint8_t id[COP_COLL_ID_BYTES], int rank, int nranks);
-
-int cop_coll_init(cop_ctx *c, const uint8_t id[COP_COLL_ID_BYTES], int rank, int nranks)
-{
-    if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return -EINVAL;
-    if (!rccl_load()) return set_err(c, -ENOSYS, "librccl not available");
-    HIPCHK(c, hipSetDevice(c->device));
-    // the communicator's set-up, its buffers (hipFree synchronises the
-    // device) and the prewarm all-reduce run with the GPU free, as every
-    // reduce does: a poll-mode kernel serving this context is paused around
-    // them (it holds every workgroup slot it could get)
-    if (int rc = pmd_pause(c)) return rc;
-    const int rc = coll_init_free(c, id, rank, nranks);
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
-}
-
 // cop_coll_init with no poll-mode kernel on the GPU
 static int coll_init_free(cop_ctx *c, const uint8_t id[COP_COLL_ID_BYTES], int rank, int nranks)
 {
@@ -2135,41 +2162,24 @@ static int coll_init_free(cop_ctx *c, const uint8_t id[COP_COLL_ID_BYTES], int r
     // the reduce's buffers at their full size now (every counter word), so
     // a reporting interval allocates nothing
     const size_t words = RULE_OFF + c->n_rule_ctr;
-    if (c->ctr_sum_words < words) {
-        if (c->ctr_sum) (void)hipFree(c->ctr_sum);
-        c->ctr_sum = nullptr;
-        c->ctr_sum_words = 0;
-        HIPCHK(c, hipMalloc(&c->ctr_sum, words * 8));
-        c->ctr_sum_words = words;
-    }
-    if (c->ctr_snap_words < words) {
-        if (c->ctr_snap) (void)hipFree(c->ctr_snap);
-        c->ctr_snap = nullptr;
-        c->ctr_snap_words = 0;
-        HIPCHK(c, hipMalloc(&c->ctr_snap, words * 8));
-        c->ctr_snap_words = words;
-    }
+    if (int rc = grow_dev(c, c->ctr_sum, c->ctr_sum_words, words)) return rc;
+    if (int rc = grow_dev(c, c->ctr_snap, c->ctr_snap_words, words)) return rc;
     r = g_rccl.all_reduce(c->counters, c->ctr_sum, 1, ncclUint64, ncclSum, c->comm, c->stream);
     if (r != ncclSuccess) return set_err(c, -EIO, "ncclAllReduce: %s", g_rccl.error_string(r));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return 0;
 }
 
-static int coll_reduce_free(cop_ctx *c, cop_counters *total, uint64_t *rule_hits, uint32_t cap, int reset);
-static int pmd_hits_sync(cop_pmd *m, uint64_t upto);
-static uint64_t pmd_refresh(cop_pmd *m, uint32_t r);
-
-int cop_coll_reduce_counters(cop_ctx *c, cop_counters *total, uint64_t *rule_hits, uint32_t cap, int reset)
+int cop_coll_init(cop_ctx *c, const uint8_t id[COP_COLL_ID_BYTES], int rank, int nranks)
 {
-    if (!c || (cap && !rule_hits)) return -EINVAL;
-    if (!c->comm) return set_err(c, -EINVAL, "cop_coll_init not called");
-    if (int rc = sync_lanes(c)) return rc;
-    // the snapshot and the all-reduce run with the GPU free (pmd_pause):
-    // RCCL's kernels need room on every rank's GPU
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = coll_reduce_free(c, total, rule_hits, cap, reset);
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
+    if (!c || !id || nranks < 1 || rank < 0 || rank >= nranks) return -EINVAL;
+    if (!rccl_load()) return set_err(c, -ENOSYS, "librccl not available");
+    HIPCHK(c, hipSetDevice(c->device));
+    // the communicator's set-up, its buffers (hipFree synchronises the
+    // device) and the prewarm all-reduce run with the GPU free, as every
+    // reduce does: a poll-mode kernel serving this context is paused around
+    // them (it holds every workgroup slot it could get)
+    return paused(c, [&]() -> int { return coll_init_free(c, id, rank, nranks); });
 }
 
 // cop_coll_reduce_counters with no poll-mode kernel on the GPU
@@ -2180,25 +2190,13 @@ static int coll_reduce_free(cop_ctx *c, cop_counters *total, uint64_t *rule_hits
     }
     const size_t shard_words = SHARD_WORDS;
     const size_t words = RULE_OFF + c->n_rule_ctr;
-    if (c->ctr_sum_words < words) {
-        if (c->ctr_sum) (void)hipFree(c->ctr_sum);
-        c->ctr_sum = nullptr;
-        c->ctr_sum_words = 0;
-        HIPCHK(c, hipMalloc(&c->ctr_sum, words * 8));
-        c->ctr_sum_words = words;
-    }
+    if (int rc = grow_dev(c, c->ctr_sum, c->ctr_sum_words, words)) return rc;
     // reset: read-and-zero every word first (an atomic exchange, so adds of
     // a poll-mode kernel running beside it land in this interval or the
     // next), then reduce that snapshot
     const unsigned long long *src = c->counters;
     if (reset) {
-        if (c->ctr_snap_words < words) {
-            if (c->ctr_snap) (void)hipFree(c->ctr_snap);
-            c->ctr_snap = nullptr;
-            c->ctr_snap_words = 0;
-            HIPCHK(c, hipMalloc(&c->ctr_snap, words * 8));
-            c->ctr_snap_words = words;
-        }
+        if (int rc = grow_dev(c, c->ctr_snap, c->ctr_snap_words, words)) return rc;
         hipError_t e = copk_snapshot(c->counters, (uint32_t)words, c->ctr_snap, 1, c->stream);
         if (e != hipSuccess) return set_err(c, -EIO, "snapshot: %s", hipGetErrorString(e));
         src = c->ctr_snap;
@@ -2218,6 +2216,16 @@ static int coll_reduce_free(cop_ctx *c, cop_counters *total, uint64_t *rule_hits
     const uint32_t k = cap < c->n_rule_ctr ? cap : c->n_rule_ctr;
     if (k) HIPCHK(c, hipMemcpy(rule_hits, c->ctr_sum + RULE_OFF, (size_t)k * 8, hipMemcpyDeviceToHost));
     return (int)c->n_rule_ctr;
+}
+
+int cop_coll_reduce_counters(cop_ctx *c, cop_counters *total, uint64_t *rule_hits, uint32_t cap, int reset)
+{
+    if (!c || (cap && !rule_hits)) return -EINVAL;
+    if (!c->comm) return set_err(c, -EINVAL, "cop_coll_init not called");
+    if (int rc = sync_lanes(c)) return rc;
+    // the snapshot and the all-reduce run with the GPU free (paused):
+    // RCCL's kernels need room on every rank's GPU
+    return paused(c, [&]() -> int { return coll_reduce_free(c, total, rule_hits, cap, reset); });
 }
 
 int cop_dev_alloc(cop_ctx *c, size_t bytes, void **dptr)
@@ -2504,16 +2512,13 @@ static int pmd_hits_sync(cop_pmd *m, uint64_t upto)
     return 0;
 }
 
-// count every completed batch's binned hits, with the GPU free (pmd_pause)
+// count every completed batch's binned hits, with the GPU free (paused)
 static int pmd_hits_flush(cop_ctx *c)
 {
     cop_pmd *m = c->pmd;
     if (!m || !m->bins) return 0;
     if (m->count_synced >= pmd_refresh(m, 0) && m->ring[0].posted.load() == m->count_synced) return 0;
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = pmd_hits_sync(m, pmd_refresh(m, 0));
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
+    return paused(c, [&]() -> int { return pmd_hits_sync(m, pmd_refresh(m, 0)); });
 }
 
 // every worker must be resident at once (static tile order): all of the
@@ -2998,10 +3003,7 @@ static int pmd_post(cop_pmd *m, uint32_t r, uint32_t count, uint32_t n_each)
         if (int rc = cop_pmd_wait_ring(m, r, need - m->n_slots)) return rc;
     if (r == 0 && m->bins && need > m->n_slots && m->count_synced < need - m->n_slots) {
         // the reused slots' binned hits are counted first, with the GPU free
-        if (int rc = pmd_pause(m->c)) return rc;
-        int rc = pmd_hits_sync(m, need - m->n_slots);
-        const int rrc = pmd_resume(m->c);
-        if (rc || rrc) return rc ? rc : rrc;
+        if (int rc = paused(m->c, [&]() -> int { return pmd_hits_sync(m, need - m->n_slots); })) return rc;
     }
     if (int rc = pmd_revive(m)) return rc;
     if (m->h_n)
@@ -3281,61 +3283,96 @@ static int live_order_end(cop_ctx *c)
     return e == hipSuccess ? 0 : set_err(c, -EIO, "update ordering: %s", hipGetErrorString(e));
 }
 
-// the poll-mode kernel's stored launch parameters: the table fields, as fill_launch sets them
-static void pmd_refresh_tables(cop_ctx *c, cop_pmd *m)
+// ---- what cop_update_* and cop_replace_* share -----------------------------------
+
+// what both work out from the stage and the table they are given
+struct LiveFacts {
+    DevLpm &t;
+    int form;         // COP_FORM_*
+    bool served;      // a live context and a stage form the device path serves: not the trie, not bucketed
+    bool want_ivt;    // the stage takes LDS interval images
+    uint32_t m_new;   // the table's intervals now
+    bool ivt_new;     // ... fit one
+};
+
+static LiveFacts live_facts(cop_ctx *c, bool is_fw, const cop_lpm_table *tab)
 {
-    CopKParams &p = m->P.k;
-    p.fw_m = m->fw_mode == COPK_TBL_IVT ? c->fw.m : 0;
-    p.fw_ib = c->fw.ib;
-    p.fw_lv = c->fw.lv;
-    p.fw_iw = m->fw_mode == COPK_TBL_IVT ? c->fw.iw : 0;
-    p.fw_starts = c->fw.starts;
-    p.fw_vals = c->fw.vals;
-    p.fw_tbl24 = c->fw.tbl24;
-    p.fw_tbl8 = c->fw.tbl8;
-    p.fw_tbl8_packed = c->fw.tbl8_packed ? 1u : 0u;
-    p.lpm_m = m->lpm_mode == COPK_TBL_IVT ? c->lpm.m : 0;
-    p.lpm_ib = c->lpm.ib;
-    p.lpm_lv = c->lpm.lv;
-    p.lpm_iw = m->lpm_mode == COPK_TBL_IVT ? c->lpm.iw : 0;
-    p.lpm_starts = c->lpm.starts;
-    p.lpm_vals = c->lpm.vals;
-    p.lpm_tbl24 = c->lpm.tbl24;
-    p.lpm_tbl8 = c->lpm.tbl8;
-    p.lpm_tbl8_packed = c->lpm.tbl8_packed ? 1u : 0u;
+    const uint32_t fl = c->cfg.flags;
+    const bool served =
+        (fl & COP_CFG_LIVE_TABLES) && !(fl & (is_fw ? COP_CFG_FW_BKT : (COP_CFG_LPM_TRIE | COP_CFG_LPM_BKT)));
+    const bool want_ivt = !(fl & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24));
+    const uint32_t m_new = is_fw ? tab->n_rv : tab->report.n_intervals;
+    return LiveFacts{is_fw ? c->fw : c->lpm, is_fw ? COP_FORM_RULE : COP_FORM_NH, served, want_ivt, m_new,
+                     want_ivt && m_new <= IVT_MAX};
+}
+
+// What the device path refuses under a poll-mode kernel, before anything is touched. The caller's
+// words: to `verb` ("update", "replace") the table, the `noun` ("update", "replacement").
+static int live_pmd_refusal(cop_ctx *c, bool is_fw, const LiveFacts &f, const char *verb, const char *noun)
+{
+    if (is_fw && (c->cfg.flags & COP_CFG_RULE_COUNTERS))
+        return set_err(c, -EBUSY, "per-rule counters: %s the firewall table with the poll-mode kernel stopped", verb);
+    // the kernel's launch geometry must stay: the stage's form and the
+    // LDS bytes of its interval image
+    uint32_t M = 0, ib = 0, iw = 0;
+    if (f.ivt_new) ivt_geometry(f.m_new, &M, &ib, &iw);
+    if (f.ivt_new != (f.t.m != 0) || (f.ivt_new && (M != f.t.m || iw != f.t.iw)))
+        return set_err(c, -EBUSY, "the %s changes the poll-mode kernel's launch geometry (cop_pmd_stop first)", noun);
+    return 0;
+}
+
+// the whole-table upload instead of the device path (cop_set_*: synchronous), reported as full
+static int live_fallback(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, const char *noun, cop_update_report *rep_out)
+{
+    if (c->pmd) return set_err(c, -EBUSY, "the %s needs a whole-table upload (cop_pmd_stop first)", noun);
+    if (int rc = is_fw ? cop_set_fw_table(c, tab) : cop_set_route_lpm(c, tab)) return rc;
+    const DevLpm &t = is_fw ? c->fw : c->lpm;
+    cop_update_report rep;
+    memset(&rep, 0, sizeof(rep));
+    rep.full = 1;
+    rep.h2d_bytes = ((uint64_t)4 << 24) + t.tbl8_bytes + (t.m ? (uint64_t)(2 * t.m + t.iw) * 4 : 0);
+    if (rep_out) *rep_out = rep;
+    return 0;
+}
+
+// apply() enqueues a table change on c->stream; this puts it in order with the readers. Under a
+// poll-mode kernel: paused, apply(), the stream drained (`sync_fail`: that failing), the kernel's stored
+// table parameters set from the stages again (whether or not apply() failed), relaunched. Otherwise
+// between live_order_begin and live_order_end; the end runs whatever failed before it, so that every
+// lane's next launch comes after whatever part of the change was enqueued. Returns the first error.
+static int live_run(cop_ctx *c, const char *sync_fail, const std::function<int()> &apply)
+{
+    if (cop_pmd *m = c->pmd)
+        return paused(c, [&]() -> int {
+            int rc = apply();
+            if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s", sync_fail);
+            set_tables(c, m->P.k, m->fw_mode, m->lpm_mode);
+            return rc;
+        });
+    int rc = live_order_begin(c);
+    if (!rc) rc = apply();
+    const int orc = live_order_end(c);
+    return rc ? rc : orc;
 }
 
 static int live_update(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_update_report *rep_out)
 {
     if (!c || !tab) return -EINVAL;
-    DevLpm &t = is_fw ? c->fw : c->lpm;
-    const int form = is_fw ? COP_FORM_RULE : COP_FORM_NH;
-    const uint32_t fl = c->cfg.flags;
     cop_update_report rep;
     memset(&rep, 0, sizeof(rep));
     if (rep_out) *rep_out = rep;
     HIPCHK(c, hipSetDevice(c->device));
-    // the whole-table upload instead: not a live context, another table (or
-    // none) in the stage, or a stage in the trie or a bucketed form
-    bool full = !(fl & COP_CFG_LIVE_TABLES) || !t.img || t.tab_uid != tab->uid ||
-                (fl & (is_fw ? COP_CFG_FW_BKT : (COP_CFG_LPM_TRIE | COP_CFG_LPM_BKT))) != 0;
-    const bool want_ivt = !(fl & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24));
-    const uint32_t m_new = is_fw ? tab->n_rv : tab->report.n_intervals;
-    const bool ivt_new = want_ivt && m_new <= IVT_MAX;
+    const LiveFacts f = live_facts(c, is_fw, tab);
+    DevLpm &t = f.t;
+    // the whole-table upload instead: not a live context, a stage in the trie
+    // or a bucketed form, or another table (or none) in the stage
+    bool full = !f.served || !t.img || t.tab_uid != tab->uid;
     cop_patch_rec *recs = nullptr;
     uint32_t n = 0;
     cop_lpm_change *chg = nullptr;
     int n_chg = 0;
-    if (c->pmd && !full) {
-        if (is_fw && (fl & COP_CFG_RULE_COUNTERS))
-            return set_err(c, -EBUSY, "per-rule counters: update the firewall table with the poll-mode kernel stopped");
-        // the kernel's launch geometry must stay: the stage's form and the
-        // LDS bytes of its interval image
-        uint32_t M = 0, ib = 0, iw = 0;
-        if (ivt_new) ivt_geometry(m_new, &M, &ib, &iw);
-        if (ivt_new != (t.m != 0) || (ivt_new && (M != t.m || iw != t.iw)))
-            return set_err(c, -EBUSY, "the update changes the poll-mode kernel's launch geometry (cop_pmd_stop first)");
-    }
+    if (c->pmd && !full)
+        if (int rc = live_pmd_refusal(c, is_fw, f, "update", "update")) return rc;
     if (!full) {
         const uint64_t g0 = cop_live_img_generation(t.img);
         n_chg = cop_lpm_changes_since(tab, g0, &chg);
@@ -3357,33 +3394,12 @@ static int live_update(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_upd
     if (full) {
         free(chg);
         free(recs);
-        if (c->pmd)
-            return set_err(c, -EBUSY, "the update needs a whole-table upload (cop_pmd_stop first)");
-        const int rc = is_fw ? cop_set_fw_table(c, tab) : cop_set_route_lpm(c, tab);
-        if (rc) return rc;
-        memset(&rep, 0, sizeof(rep));
-        rep.full = 1;
-        rep.h2d_bytes = ((uint64_t)4 << 24) + t.tbl8_bytes + (t.m ? (uint64_t)(2 * t.m + t.iw) * 4 : 0);
-        if (rep_out) *rep_out = rep;
-        return 0;
+        return live_fallback(c, is_fw, tab, "update", rep_out);
     }
     int rc = live_setup(c);
-    if (!rc && c->pmd) {
-        cop_pmd *m = c->pmd;
-        if ((rc = pmd_pause(c)) == 0) {
-            rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
-            if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "patch sync");
-            pmd_refresh_tables(c, m);
-            const int rrc = pmd_resume(c);
-            if (!rc) rc = rrc;
-        }
-    } else if (!rc) {
-        rc = live_order_begin(c);
-        if (!rc) rc = live_apply(c, t, tab, form, ivt_new, recs, n, chg, n_chg, &rep);
-        // every lane's next launch comes after whatever part of the patch was enqueued
-        const int orc = live_order_end(c);
-        if (!rc) rc = orc;
-    }
+    if (!rc)
+        rc = live_run(c, "patch sync",
+                      [&]() -> int { return live_apply(c, t, tab, f.form, f.ivt_new, recs, n, chg, n_chg, &rep); });
     free(chg);
     free(recs);
     if (rc) {
@@ -3417,13 +3433,6 @@ int cop_update_route_lpm(cop_ctx *c, const cop_lpm_table *t, cop_update_report *
 // and retired (c->retired), since launches queued earlier still read it.
 
 static_assert(COP_PAINT_CHUNK == COPK_PAINT_CHUNK, "the host mirror paints the kernel's chunks");
-
-// the tbl8 capacity (groups) of a live image of a table: upload_lpm's rule
-static uint32_t live_grp_cap(const cop_lpm_table *tab, uint32_t n_ext)
-{
-    return (uint32_t)std::max<uint64_t>(
-        std::max(n_ext, 1u), std::min<uint64_t>(2 * (uint64_t)tab->cfg.number_tbl8s, (uint64_t)n_ext + std::max(256u, n_ext / 2)));
-}
 
 // the paint kernel's inputs in one buffer: starts | entries | ext24, each
 // padded to 16 bytes
@@ -3515,44 +3524,26 @@ static int replace_apply(cop_ctx *c, DevLpm &t, const cop_lpm_table *tab, int fo
 static int live_replace(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_update_report *rep_out)
 {
     if (!c || !tab) return -EINVAL;
-    DevLpm &t = is_fw ? c->fw : c->lpm;
-    const int form = is_fw ? COP_FORM_RULE : COP_FORM_NH;
-    const uint32_t fl = c->cfg.flags;
     cop_update_report rep;
     memset(&rep, 0, sizeof(rep));
     if (rep_out) *rep_out = rep;
     HIPCHK(c, hipSetDevice(c->device));
+    const LiveFacts f = live_facts(c, is_fw, tab);
+    DevLpm &t = f.t;
     // the device path paints the LDS interval and DIR-24-8 forms of a live
     // context; a firewall stage with per-rule counters needs its counter
     // words to cover the new table's ids already (growing them waits)
-    bool dev = (fl & COP_CFG_LIVE_TABLES) && !(fl & (is_fw ? COP_CFG_FW_BKT : (COP_CFG_LPM_TRIE | COP_CFG_LPM_BKT)));
-    if (dev && is_fw && (fl & COP_CFG_RULE_COUNTERS) &&
+    bool dev = f.served;
+    if (dev && is_fw && (c->cfg.flags & COP_CFG_RULE_COUNTERS) &&
         c->n_rule_ctr < std::max(tab->n_rules, std::min(tab->cfg.max_rules, COP_LPM_NH_MASK + 1u)))
         dev = false;
-    if (!dev) {
-        if (c->pmd) return set_err(c, -EBUSY, "the replacement needs a whole-table upload (cop_pmd_stop first)");
-        const int rc = is_fw ? cop_set_fw_table(c, tab) : cop_set_route_lpm(c, tab);
-        if (rc) return rc;
-        rep.full = 1;
-        rep.h2d_bytes = ((uint64_t)4 << 24) + t.tbl8_bytes + (t.m ? (uint64_t)(2 * t.m + t.iw) * 4 : 0);
-        if (rep_out) *rep_out = rep;
-        return 0;
-    }
-    const bool want_ivt = !(fl & (is_fw ? COP_CFG_FW_FORCE_DIR24 : COP_CFG_LPM_FORCE_DIR24));
-    const uint32_t m_new = is_fw ? tab->n_rv : tab->report.n_intervals;
-    const bool ivt_new = want_ivt && m_new <= IVT_MAX;
-    if (c->pmd) {
-        if (is_fw && (fl & COP_CFG_RULE_COUNTERS))
-            return set_err(c, -EBUSY, "per-rule counters: replace the firewall table with the poll-mode kernel stopped");
-        // the kernel's launch geometry must stay, as for cop_update_*
-        uint32_t M = 0, ib = 0, iw = 0;
-        if (ivt_new) ivt_geometry(m_new, &M, &ib, &iw);
-        if (ivt_new != (t.m != 0) || (ivt_new && (M != t.m || iw != t.iw)))
-            return set_err(c, -EBUSY, "the replacement changes the poll-mode kernel's launch geometry (cop_pmd_stop first)");
-    }
+    if (!dev) return live_fallback(c, is_fw, tab, "replacement", rep_out);
+    if (c->pmd)
+        if (int rc = live_pmd_refusal(c, is_fw, f, "replace", "replacement")) return rc;
     PaintPlan P;
-    if (int rc = paint_plan(c, tab, form, P)) return rc;
-    const uint32_t grp_cap = live_grp_cap(tab, P.n_ext);
+    if (int rc = paint_plan(c, tab, f.form, P)) return rc;
+    // upload_lpm's rule for a live image's tbl8 capacity, but never without a group
+    const uint32_t grp_cap = (uint32_t)std::max<uint64_t>(std::max(P.n_ext, 1u), live_spare_cap(tab, P.n_ext));
     if (int rc = live_setup(c)) return rc;
     if (int rc = paint_stage(c, P)) return rc;
     // what is missing or outgrown, before anything is enqueued: a first tbl24,
@@ -3567,7 +3558,7 @@ static int live_replace(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_up
     hipError_t e = hipSuccess;
     if (!t.tbl24) e = hipMalloc(&n24, (size_t)4 << 24);
     if (e == hipSuccess && (!t.tbl8 || t.tbl8_packed || t.tbl8_bytes < tbl8_need)) e = hipMalloc(&n8, tbl8_need);
-    if (e == hipSuccess && want_ivt && !ivt_room) {
+    if (e == hipSuccess && f.want_ivt && !ivt_room) {
         e = hipMalloc(&ns, (size_t)(IVT_MAX + IVT_IW_MAX) * 4);
         if (e == hipSuccess) e = hipMalloc(&nv, (size_t)IVT_MAX * 4);
     }
@@ -3576,49 +3567,41 @@ static int live_replace(cop_ctx *c, bool is_fw, const cop_lpm_table *tab, cop_up
         return set_err(c, -ENOMEM, "replacement buffers: %s", hipGetErrorString(e));
     }
     const uint32_t groups_before = t.img ? cop_live_img_groups_used(t.img) : (t.has_table ? t.n_ext : 0u);
-    cop_live_img *book = cop_live_img_create(tab, form, grp_cap);
+    cop_live_img *book = cop_live_img_create(tab, f.form, grp_cap);
     if (!book) {
         drop_new();
         return set_err(c, -ENOMEM, "live table book");
     }
-    int rc = c->pmd ? pmd_pause(c) : 0;
-    if (rc) {
+    bool committed = false;
+    const int rc = live_run(c, "paint sync", [&]() -> int {
+        // from here on the stage changes: launches made after this call read the new fields
+        if (n24) t.tbl24 = n24;
+        if (n8) {
+            if (t.tbl8) c->retired.push_back({t.tbl8, false});
+            t.tbl8 = n8;
+            t.tbl8_bytes = tbl8_need;
+            t.tbl8_packed = false;
+        }
+        if (ns) {
+            if (t.starts) c->retired.push_back({t.starts, false});
+            if (t.vals) c->retired.push_back({t.vals, false});
+            t.starts = ns;
+            t.vals = nv;
+        }
+        cop_live_img_free(t.img);
+        t.img = book;
+        t.tab_uid = tab->uid;
+        t.grp_cap = grp_cap;
+        t.n_ext = P.n_ext;
+        t.loaded = true;
+        t.has_table = true;
+        committed = true;
+        return replace_apply(c, t, tab, f.form, f.ivt_new, P, grp_cap, &rep);
+    });
+    if (!committed) {   // the pause (or the ordering) failed: nothing enqueued, the stage keeps what it had
         drop_new();
         cop_live_img_free(book);
         return rc;
-    }
-    // from here on the stage changes: launches made after this call read the new fields
-    if (n24) t.tbl24 = n24;
-    if (n8) {
-        if (t.tbl8) c->retired.push_back({t.tbl8, false});
-        t.tbl8 = n8;
-        t.tbl8_bytes = tbl8_need;
-        t.tbl8_packed = false;
-    }
-    if (ns) {
-        if (t.starts) c->retired.push_back({t.starts, false});
-        if (t.vals) c->retired.push_back({t.vals, false});
-        t.starts = ns;
-        t.vals = nv;
-    }
-    cop_live_img_free(t.img);
-    t.img = book;
-    t.tab_uid = tab->uid;
-    t.grp_cap = grp_cap;
-    t.n_ext = P.n_ext;
-    t.loaded = true;
-    t.has_table = true;
-    if (c->pmd) {
-        rc = replace_apply(c, t, tab, form, ivt_new, P, grp_cap, &rep);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "paint sync");
-        pmd_refresh_tables(c, c->pmd);
-        const int rrc = pmd_resume(c);
-        if (!rc) rc = rrc;
-    } else {
-        rc = live_order_begin(c);
-        if (!rc) rc = replace_apply(c, t, tab, form, ivt_new, P, grp_cap, &rep);
-        const int orc = live_order_end(c);
-        if (!rc) rc = orc;
     }
     if (rc) {
         // the image may be painted in part: the next update or replacement starts afresh
@@ -3755,11 +3738,8 @@ int cop_lookup_bulk(cop_ctx *c, uint32_t stage, const uint32_t *ips, uint32_t n,
     if (c->pmd) {
         // another kernel is not guaranteed a place beside the poll-mode
         // kernel: pause it, look up on the free GPU, relaunch it
-        if (int rc = pmd_pause(c)) return rc;
-        int rc = lookup_launch(c, c->stream, *t, form, mask, ips, n, out);
-        if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "lookup sync");
-        const int rrc = pmd_resume(c);
-        return rc ? rc : rrc;
+        return paused_op(c, "lookup sync",
+                         [&]() -> int { return lookup_launch(c, c->stream, *t, form, mask, ips, n, out); });
     }
     Lane &L = c->lane[c->next_lane];
     c->next_lane = (c->next_lane + 1) % c->n_lanes;
@@ -3779,42 +3759,42 @@ static int lookup_host_run(cop_ctx *c, DevLpm &t, int form, uint32_t mask, const
         if (!S.d) HIPCHK(c, hipMalloc(&S.d, (size_t)COP_LOOKUP_STAGE_WORDS * 4));
         if (!S.done) HIPCHK(c, hipEventCreateWithFlags(&S.done, hipEventDisableTiming));
     }
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = 0;
-    auto drain = [&](LookupStage &S) {
-        if (!S.n) return;
-        if (hipEventSynchronize(S.done) != hipSuccess) {
-            if (!rc) rc = set_err(c, -EIO, "lookup staging: wait failed");
-        } else if (!rc) {
-            memcpy(out + S.first, S.h, (size_t)S.n * 4);
+    return paused(c, [&]() -> int {
+        int rc = 0;
+        auto drain = [&](LookupStage &S) {
+            if (!S.n) return;
+            if (hipEventSynchronize(S.done) != hipSuccess) {
+                if (!rc) rc = set_err(c, -EIO, "lookup staging: wait failed");
+            } else if (!rc) {
+                memcpy(out + S.first, S.h, (size_t)S.n * 4);
+            }
+            S.n = 0;
+        };
+        uint64_t done = 0;
+        for (uint32_t k = 0; done < n && !rc; k++) {
+            LookupStage &S = c->lookup_stage[k & 1u];
+            drain(S);
+            if (rc) break;
+            const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - done, COP_LOOKUP_STAGE_WORDS);
+            memcpy(S.h, ips + done, (size_t)cnt * 4);
+            hipStream_t s = c->pmd ? c->stream : c->lane[k % (uint32_t)c->n_lanes].s;
+            hipError_t e = hipMemcpyAsync(S.d, S.h, (size_t)cnt * 4, hipMemcpyHostToDevice, s);
+            if (e == hipSuccess) {
+                rc = lookup_launch(c, s, t, form, mask, S.d, cnt, S.d);
+                if (!rc) e = hipMemcpyAsync(S.h, S.d, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
+            }
+            // (the event is recorded whatever was enqueued, so the slot can be waited for)
+            const hipError_t e2 = hipEventRecord(S.done, s);
+            if ((e != hipSuccess || e2 != hipSuccess) && !rc)
+                rc = set_err(c, -EIO, "lookup staging: %s", hipGetErrorString(e != hipSuccess ? e : e2));
+            S.first = done;
+            S.n = e2 == hipSuccess ? cnt : 0;
+            done += cnt;
         }
-        S.n = 0;
-    };
-    uint64_t done = 0;
-    for (uint32_t k = 0; done < n && !rc; k++) {
-        LookupStage &S = c->lookup_stage[k & 1u];
-        drain(S);
-        if (rc) break;
-        const uint32_t cnt = (uint32_t)std::min<uint64_t>(n - done, COP_LOOKUP_STAGE_WORDS);
-        memcpy(S.h, ips + done, (size_t)cnt * 4);
-        hipStream_t s = c->pmd ? c->stream : c->lane[k % (uint32_t)c->n_lanes].s;
-        hipError_t e = hipMemcpyAsync(S.d, S.h, (size_t)cnt * 4, hipMemcpyHostToDevice, s);
-        if (e == hipSuccess) {
-            rc = lookup_launch(c, s, t, form, mask, S.d, cnt, S.d);
-            if (!rc) e = hipMemcpyAsync(S.h, S.d, (size_t)cnt * 4, hipMemcpyDeviceToHost, s);
-        }
-        // (the event is recorded whatever was enqueued, so the slot can be waited for)
-        const hipError_t e2 = hipEventRecord(S.done, s);
-        if ((e != hipSuccess || e2 != hipSuccess) && !rc)
-            rc = set_err(c, -EIO, "lookup staging: %s", hipGetErrorString(e != hipSuccess ? e : e2));
-        S.first = done;
-        S.n = e2 == hipSuccess ? cnt : 0;
-        done += cnt;
-    }
-    // the older slot first (its words sit earlier in out; order is irrelevant to correctness)
-    for (auto &S : c->lookup_stage) drain(S);
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
+        // the older slot first (its words sit earlier in out; order is irrelevant to correctness)
+        for (auto &S : c->lookup_stage) drain(S);
+        return rc;
+    });
 }
 
 int cop_lookup_bulk_host(cop_ctx *c, uint32_t stage, const uint32_t *ips, uint64_t n, uint32_t *out)
@@ -3880,19 +3860,8 @@ int cop_lookup_audit(cop_ctx *c, uint32_t stage, const cop_lpm_table *tab, cop_a
 // alone, never grown: launches of one lane run in order, so the next call of
 // the kind overwrites it only after this one's last kernel has read it.
 
-// Between pmd_pause and pmd_resume: op() queues on c->stream (0, or an error it has set), then the
-// stream is drained; `fail` is the error of a drain that failed.
-static int paused_op(cop_ctx *c, const char *fail, const std::function<int()> &op)
-{
-    if (int rc = pmd_pause(c)) return rc;
-    int rc = op();
-    if (!rc && hipStreamSynchronize(c->stream) != hipSuccess) rc = set_err(c, -EIO, "%s", fail);
-    const int rrc = pmd_resume(c);
-    return rc ? rc : rrc;
-}
-
 // Runs launch(lane, stream) as a side call: asynchronous on the next lane behind every lane's queued
-// work, or synchronous between pmd_pause and pmd_resume on the side stream.
+// work, or synchronous between pmd_pause and pmd_resume on the side stream (paused_op).
 static int side_run(cop_ctx *c, const char *what, const std::function<int(int, hipStream_t)> &launch)
 {
     HIPCHK(c, hipSetDevice(c->device));
@@ -4126,12 +4095,12 @@ static int devobj_destroy(cop_ctx *c, std::vector<T *> &reg, T *obj, const char 
     if (int rc = devobj_of(c, reg, obj, what, kind)) return rc;
     if (int rc = sync_lanes(c)) return rc;   // queued work may use the memory
     // beside a poll-mode kernel every side call has completed on return, and hipFree must not wait for it
-    if (int rc = pmd_pause(c)) return rc;
-    (void)hipFree(mem(obj));
-    const int rrc = pmd_resume(c);
-    reg.erase(std::find(reg.begin(), reg.end(), obj));
-    delete obj;
-    return rrc;
+    return paused(c, [&]() -> int {
+        (void)hipFree(mem(obj));
+        reg.erase(std::find(reg.begin(), reg.end(), obj));
+        delete obj;
+        return 0;
+    });
 }
 }  // extern "C++"
 

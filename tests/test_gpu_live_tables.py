@@ -391,6 +391,66 @@ def test_update_under_the_poll_mode_kernel(gpu_ctx_factory, monkeypatch):
     assert np.array_equal(res["verdict"], ctx2[0]["verdict"]) and (res["verdict"] == cg.FORWARD).all()
 
 
+def test_rule_counters_refuse_table_changes_under_the_poll_mode_kernel(gpu_ctx_factory, monkeypatch):
+    """fw1k in LDS with per-rule counters, a 2-slot ring of 4096-packet
+    batches. With the kernel serving, an update (one rule added) and a
+    replacement (every action flipped) are both refused with -EBUSY before the
+    kernel is paused, and both slots are served by the table as first set.
+    With the kernel stopped the same update and the same replacement go down
+    the device path and the stage audits clean against each table."""
+    monkeypatch.delenv("COP_PPT", raising=False)
+    rules = cg.gen_rules(0x5EED1002, 1000, cg.GEN_FW, 20)
+    flipped = rules.copy()
+    flipped["next_hop"] = np.where(rules["next_hop"] != 0, 0, 1)
+    a, b = cg.LpmTable(rules, 1024, 24, True), cg.LpmTable(flipped, 1024, 24, True)
+    m = Model(a, 1024, 24, rules=rules)
+    new = cg.prefixes([0xC6336400], [24], [1])
+    B = 4096
+    rest = le.subsample(le.boundary_probes(a.rules()), B - 6 * len(new) - 4)
+    pk = le.probe_frames(le.pad_to(np.unique(np.concatenate([le.boundary_probes(new), rest])), B)[:B])
+    ctx = gpu_ctx_factory(stages=F, flags=LIVE | cg.CFG_RULE_COUNTERS | cg.CFG_SEG_LISTS, max_batch=B)
+    ctx.set_fw_table(a)
+    dp = ctx.alloc(2 * B * 64)
+    dp.upload(np.concatenate([pk, pk]))
+    dr, df, dc = ctx.alloc(2 * B * 8), ctx.alloc(2 * B * 4), ctx.alloc(2 * nseg(B) * 4 + 16)
+    dr.fill(0xAB)
+    ring = cg.make_ring(dp, 2, B, dr, B * 64, stride=64, fwd_idx=df, fwd_count=dc)
+
+    def slot(s):
+        res = dr.download(cg.RESULT_DT, 2 * B)[s * B:(s + 1) * B]
+        fwd = df.download(np.uint32, 2 * B)[s * B:(s + 1) * B]
+        cnt = dc.download(np.uint32, 2 * nseg(B))[s * nseg(B):(s + 1) * nseg(B)]
+        return res, seg_to_dense(fwd, cnt, B)
+
+    def audit(tab):
+        rep, bad = ctx.lookup_audit(F, tab, bad_cap=8)
+        assert rep["n_mismatch"] == 0 and rep["stale"] == 0 and rep["n_probes"] > 0, (rep, bad)
+
+    e0 = expect(pk, B, F, m, None)
+    with ctx.pmd_start(ring) as pm:
+        pm.post(1)
+        pm.wait()
+        m.add(int(new["ip"][0]), int(new["depth"][0]), int(new["next_hop"][0]))
+        before = pm.info()["launches"]
+        for change, tab in ((ctx.update_fw_table, a), (ctx.replace_fw_table, b)):
+            with pytest.raises(cg.CopError) as err:
+                change(tab)
+            assert err.value.code == EBUSY and "per-rule counters" in str(err.value), str(err.value)
+        assert pm.info()["launches"] == before                   # nothing was paused
+        pm.post(1)
+        pm.wait()
+        assert pm.info()["completed"] == 2
+    eb = expect(pk, B, F, Model(b, 1024, 24, rules=flipped), None)
+    assert (e0[0]["verdict"] != eb[0]["verdict"]).sum() >= 100   # a replacement that got through would show
+    assert_parity(*slot(0), e0[0], e0[1])
+    assert_parity(*slot(1), e0[0], e0[1])
+    # with the kernel stopped both changes take the device path
+    assert ctx.update_fw_table(a)["full"] == 0
+    audit(a)
+    assert ctx.replace_fw_table(b)["full"] == 0
+    audit(b)
+
+
 # ---- j. fallbacks ---------------------------------------------------------------
 @pytest.mark.parametrize("case", ["not_live", "route_bkt", "foreign_table"])
 def test_update_falls_back_to_the_whole_upload(gpu_ctx_factory, monkeypatch, case):
