@@ -173,6 +173,25 @@ class FwdRwDesc(Structure):
     _fields_ = [("port", c_void_p * MAX_DEMUX_PORTS), ("status", c_void_p * MAX_DEMUX_PORTS)]
 
 
+ACL_MAX_RULES = 1024     # COP_ACL_MAX_RULES
+ACL_HIT, ACL_DROP, ACL_SKIP = 0x01000000, 0x04000000, 0x08000000   # COP_ACL_*
+ACL_COUNTERS = 0x1       # cop_acl_create flag
+ACL_RULE_DT = np.dtype([("src_ip", "<u4"), ("dst_ip", "<u4"), ("sport_lo", "<u2"), ("sport_hi", "<u2"),
+                        ("dport_lo", "<u2"), ("dport_hi", "<u2"), ("src_depth", "u1"), ("dst_depth", "u1"),
+                        ("proto", "u1"), ("proto_mask", "u1"), ("priority", "<i4"), ("action", "<u4")])
+ACL_KEY_DT = np.dtype([("src", "<u4"), ("dst", "<u4"), ("sport", "<u2"), ("dport", "<u2"), ("proto", "u1"),
+                       ("_pad", "u1", (3,))])
+
+
+class AclReport(Structure):
+    _fields_ = [("n_rules", c_uint32), ("n_intervals", c_uint32 * 4), ("row_words", c_uint32),
+                ("first_error_idx", c_uint32), ("_pad", c_uint32), ("image_bytes", c_uint64)]
+
+
+class AclDesc(Structure):
+    _fields_ = [("words", c_void_p), ("out_idx", c_void_p), ("out_count", c_void_p), ("status", c_void_p)]
+
+
 class TraceOpts(Structure):
     _fields_ = [("n_ports", c_uint32), ("pct_non_ipv4", c_uint32), ("pct_bad_version", c_uint32),
                 ("pct_unknown_dst", c_uint32), ("pct_vport_dst", c_uint32),
@@ -305,6 +324,20 @@ SIGNATURES = {
     "cop_fwd_rewrite_host": (c_int, [c_void_p, c_uint32, POINTER(FwdConfig), POINTER(Batch), POINTER(TxDesc),
                                      POINTER(FwdRwDesc), c_uint32, c_uint32, c_int, c_uint32]),
     "cop_ipv4_csum_host": (ctypes.c_uint16, [c_void_p]),
+    "cop_acl_build": (c_int, [c_void_p, c_uint32, POINTER(c_void_p), POINTER(AclReport)]),
+    "cop_acl_free": (None, [c_void_p]),
+    "cop_acl_match_host": (c_int, [c_void_p, c_void_p, c_uint32, c_void_p]),
+    "cop_acl_create": (c_int, [c_void_p, c_void_p, c_uint32, POINTER(c_void_p)]),
+    "cop_acl_set": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "cop_acl_destroy": (c_int, [c_void_p, c_void_p]),
+    "cop_acl_counters_read": (c_int, [c_void_p, c_void_p, c_void_p, c_uint32, c_int]),
+    "cop_acl_device_ptr": (c_int, [c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p),
+                                   POINTER(c_uint32)]),
+    "cop_acl_classify": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(AclDesc), c_uint32]),
+    "cop_acl_filter": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(AclDesc), c_uint32]),
+    "cop_acl_classify_host": (c_int, [c_void_p, POINTER(Batch), POINTER(AclDesc), c_uint32, c_uint32]),
+    "cop_acl_filter_host": (c_int, [c_void_p, c_void_p, POINTER(Batch), POINTER(AclDesc), c_uint32, c_uint32, c_int,
+                                    c_uint32]),
     "cop_dev_alloc": (c_int, [c_void_p, c_size_t, POINTER(c_void_p)]),
     "cop_dev_alloc_ex": (c_int, [c_void_p, c_size_t, c_uint32, POINTER(c_void_p)]),
     "cop_dev_free": (c_int, [c_void_p, c_void_p]),
@@ -1052,6 +1085,10 @@ class Context:
         """cop_neigh_create: a neighbour table of n_entries entries on this context, all invalid."""
         return Neigh(self, n_entries)
 
+    def acl(self, table: "AclTable", flags: int = 0) -> "Acl":
+        """cop_acl_create: the built table's image on this context (ACL_COUNTERS: a hit counter per rule)."""
+        return Acl(self, table, flags)
+
     def fwd_check(self, neigh: "Neigh", cfg: "FwdConfig", batches, descs):
         """cop_fwd_check: the batches' forward lists filtered into the lists of `descs` (one FwdCheckDesc per
         batch, make_fwd_check). Asynchronous: valid after sync(); synchronous beside a poll-mode kernel."""
@@ -1517,6 +1554,117 @@ def ipv4_csum_host(hdr) -> int:
     a = np.ascontiguousarray(hdr, dtype=np.uint8)
     assert a.size == 20
     return int(lib().cop_ipv4_csum_host(a.ctypes.data))
+
+
+def acl_rules(n: int) -> np.ndarray:
+    """n zeroed rules (ACL_RULE_DT) that match everything: depth 0, any protocol, ports 0..65535."""
+    r = np.zeros(n, dtype=ACL_RULE_DT)
+    r["sport_hi"] = r["dport_hi"] = 0xFFFF
+    return r
+
+
+class AclTable:
+    """A built ACL image (cop_acl_build; host only). Raises CopError with .report set on a bad rule set."""
+
+    def __init__(self, rules: np.ndarray, n: int | None = None):
+        rules = np.ascontiguousarray(rules, dtype=ACL_RULE_DT)
+        self.handle, self.report = c_void_p(), AclReport()
+        rc = lib().cop_acl_build(rules.ctypes.data if len(rules) else None, len(rules) if n is None else n,
+                                 byref(self.handle), byref(self.report))
+        if rc < 0:
+            e = CopError(rc, "acl_build")
+            e.report = self.report
+            raise e
+        self.n_rules = self.report.n_rules
+
+    def free(self):
+        if self.handle:
+            h, self.handle = self.handle, c_void_p()
+            lib().cop_acl_free(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def match(self, keys: np.ndarray) -> np.ndarray:
+        """cop_acl_match_host: the word of every key (ACL_KEY_DT)."""
+        keys = np.ascontiguousarray(keys, dtype=ACL_KEY_DT)
+        out = np.zeros(len(keys), dtype=np.uint32)
+        rc = lib().cop_acl_match_host(self.handle, keys.ctypes.data, len(keys), out.ctypes.data)
+        if rc < 0:
+            raise CopError(rc, "acl_match_host")
+        return out
+
+
+class Acl:
+    """A context's ACL (cop_acl_*). classify() and filter() are asynchronous (valid after
+    ctx.sync()); synchronous beside a poll-mode kernel."""
+
+    def __init__(self, ctx: "Context", table: AclTable, flags: int = 0):
+        self.ctx, self.handle, self.flags = ctx, c_void_p(), flags
+        _check(lib().cop_acl_create(ctx.handle, table.handle, flags, byref(self.handle)), ctx, "acl_create")
+        self.n_rules = table.n_rules
+
+    def set(self, table: AclTable):
+        _check(lib().cop_acl_set(self.ctx.handle, self.handle, table.handle), self.ctx, "acl_set")
+        self.n_rules = table.n_rules
+
+    def destroy(self):
+        if self.handle:
+            h, self.handle = self.handle, c_void_p()
+            _check(lib().cop_acl_destroy(self.ctx.handle, h), self.ctx, "acl_destroy")
+
+    def classify(self, batches, descs):
+        assert len(batches) == len(descs)
+        arr, darr = (Batch * len(batches))(*batches), (AclDesc * len(descs))(*descs)
+        _check(lib().cop_acl_classify(self.ctx.handle, self.handle, arr, darr, len(batches)), self.ctx, "acl_classify")
+
+    def filter(self, batches, descs):
+        assert len(batches) == len(descs)
+        arr, darr = (Batch * len(batches))(*batches), (AclDesc * len(descs))(*descs)
+        _check(lib().cop_acl_filter(self.ctx.handle, self.handle, arr, darr, len(batches)), self.ctx, "acl_filter")
+
+    def counters(self, reset: bool = False, cap: int | None = None) -> np.ndarray:
+        """cop_acl_counters_read: one u64 per rule index (synchronous)."""
+        cap = self.n_rules if cap is None else cap
+        out = np.zeros(max(cap, 1), dtype=np.uint64)
+        rc = _check(lib().cop_acl_counters_read(self.ctx.handle, self.handle, out.ctypes.data, cap, 1 if reset else 0),
+                    self.ctx, "acl_counters_read")
+        return out[:min(cap, rc)]
+
+    def device_ptr(self):
+        """(device address of the image, its bytes, device address of the counters or None, n_rules)."""
+        img, nbytes, ctr, n = c_void_p(), c_uint64(), c_void_p(), c_uint32()
+        _check(lib().cop_acl_device_ptr(self.ctx.handle, self.handle, byref(img), byref(nbytes), byref(ctr), byref(n)),
+               self.ctx, "acl_device_ptr")
+        return img.value, nbytes.value, ctr.value, n.value
+
+
+def make_acl_desc(words=None, out_idx=None, out_count=None, status=None) -> AclDesc:
+    """A batch's cop_acl_desc (DeviceBuffer, address or None each): words for classify, the rest for filter."""
+    a = lambda x: x.addr if isinstance(x, DeviceBuffer) else x
+    d = AclDesc()
+    d.words, d.out_idx, d.out_count, d.status = a(words), a(out_idx), a(out_count), a(status)
+    d._keep = tuple(x for x in (words, out_idx, out_count, status) if isinstance(x, DeviceBuffer))
+    return d
+
+
+def acl_classify_host(table: AclTable, batches, descs, max_batch: int = 0) -> int:
+    """cop_acl_classify_host over host memory (every pointer a host address). Returns the C code."""
+    assert len(batches) == len(descs)
+    arr, darr = (Batch * len(batches))(*batches), (AclDesc * len(descs))(*descs)
+    return lib().cop_acl_classify_host(table.handle, arr, darr, len(batches), max_batch)
+
+
+def acl_filter_host(table: AclTable, counters, batches, descs, n_lists: int = 1, seg: bool = False,
+                    max_batch: int = 0) -> int:
+    """cop_acl_filter_host; counters: n_rules u64 or None."""
+    assert len(batches) == len(descs)
+    arr, darr = (Batch * len(batches))(*batches), (AclDesc * len(descs))(*descs)
+    return lib().cop_acl_filter_host(table.handle, None if counters is None else counters.ctypes.data, arr, darr,
+                                     len(batches), n_lists, 1 if seg else 0, max_batch)
 
 
 def make_tx(out, lens=None, copy_bytes: int = 0, slot_bytes: int = 0) -> TxDesc:

@@ -303,6 +303,31 @@ int cop_fwd_rewrite_validate(const void *entries, uint32_t n_entries, const cop_
                              const cop_batch *batches, const cop_tx_desc *tx, const cop_fwd_rw_desc *rw, uint32_t nb,
                              uint32_t n_lists, int seg, uint32_t max_batch, const char **why);
 
+/* ---- ACL (acl.c, cop_acl.hip) ------------------------------------------------ */
+/* Where the parts of a built image lie, in u32 words from its start (acl.c's
+ * head comment; every offset is a multiple of 4): per range field (src, dst,
+ * sport, dport) niv starts and niv rows of row_words, the 256 protocol rows,
+ * the rank -> word table. */
+typedef struct cop_acl_layout {
+    uint32_t n_rules, row_words;
+    uint32_t niv[4], off_starts[4], off_rows[4];
+    uint32_t off_proto, off_rank;
+    uint32_t words;   /* the whole image */
+    uint32_t _pad;
+} cop_acl_layout;
+struct cop_acl_table {
+    cop_acl_layout lay;
+    uint32_t *image;
+};
+/* The argument checks cop_acl_classify / cop_acl_filter and the host mirror
+ * share (include/cop_gpu.h "ACL"): image and counters (or NULL) device or
+ * host, only their extents are used; filter != 0 for the filter, whose list
+ * layout n_lists / seg is; max_batch 0 for no limit on n. 0, or -EINVAL /
+ * -ENOMEM with *why (may be NULL) the reason. */
+int cop_acl_validate(const void *image, uint64_t image_bytes, const void *counters, uint32_t n_rules,
+                     const cop_batch *batches, const cop_acl_desc *descs, uint32_t nb, int filter, uint32_t n_lists,
+                     int seg, uint32_t max_batch, const char **why);
+
 /* Host paths with an explicit stage mask instead of the context's: the
  * drop-in coprocessor API (dropin.c) runs the coprocessor thread's NF chain,
  * COP_DROPIN_STAGES (process_packet, coprocessor.c:50-65). */

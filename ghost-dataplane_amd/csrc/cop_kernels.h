@@ -411,9 +411,65 @@ struct CopKFwd {
     uint32_t seg;
 };
 
+// cop_acl_words / cop_acl_mark / cop_acl_write (cop_acl.hip): the 5-tuple ACL
+// (cop_acl_classify, cop_acl_filter). The image is acl.c's: per range field
+// niv sorted starts and niv rows of row_words u32, 256 protocol rows and the
+// rank -> word table, at word offsets that are multiples of 4. A workgroup
+// stages the four starts arrays in LDS (dynamic: them, five row offsets and
+// one rank per packet; the filter with counters also pad4(n_rules) words, the
+// chunk's hits per rule, summed there and added to `counters` once per rule).
+// Classify: one CopKAclBatch per batch, one workgroup
+// per COPK_ACL_CHUNK packets. Filter: one CopKAclList per forward list on the
+// chunk grid of cop_chunk.h; scratch per chunk, COPK_ACL_SCRATCH_WORDS words
+// from (scratch_begin + chunk_begin + c): words 0..12 the mark record, 16..19
+// the waves' kept-as-miss counts, 20..23 their kept-as-skip counts.
+#define COPK_ACL_MAXB 32
+#define COPK_ACL_MAXL 32
+#define COPK_ACL_CHUNK 256
+#define COPK_ACL_SCRATCH_WORDS 24
+struct CopKAclTab {
+    const uint32_t *image;         // 16-byte aligned
+    unsigned long long *counters;  // filter: one per rule index, or null
+    uint32_t n_rules, row_words;
+    uint32_t niv[4], off_starts[4], off_rows[4];
+    uint32_t off_proto, off_rank;
+};
+struct CopKAclBatch {
+    const uint8_t *pkts;       // batch pkts + data_off
+    const uint32_t *offsets;   // IMIX: byte offset of packet i; else null
+    uint32_t *words;           // n words
+    uint32_t n;
+    uint32_t stride;
+    uint32_t chunk_begin;      // first workgroup of this batch
+    uint32_t _pad;
+};
+struct CopKAclWords {
+    CopKAclTab tab;
+    CopKAclBatch b[COPK_ACL_MAXB];
+    uint32_t nb;
+    uint32_t nchunks;          // the grid
+};
+struct CopKAclList {
+    CopKListHead h;
+    uint32_t *out_idx;         // the same position of the output layout
+    uint32_t *out_count;
+    uint32_t *status;          // 16-byte aligned, 4 words
+};
+struct CopKAcl {
+    CopKAclTab tab;
+    CopKAclList l[COPK_ACL_MAXL];
+    uint32_t *scratch;         // context-owned
+    uint32_t scratch_begin;    // in chunks
+    uint32_t nl;
+    uint32_t nchunks;          // the grid
+    uint32_t seg;
+};
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+hipError_t copk_acl_words_launch(const CopKAclWords *p, hipStream_t stream);
+hipError_t copk_acl_filter_launch(const CopKAcl *p, hipStream_t stream);
 hipError_t copk_fwd_check_launch(const CopKFwd *p, hipStream_t stream);
 hipError_t copk_fwd_rewrite_launch(const CopKFwd *p, hipStream_t stream);
 // seal: keystream, MAC, status; open: MAC (writes ok), keystream under ok, status; poly: MAC, status

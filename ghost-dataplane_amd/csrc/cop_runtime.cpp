@@ -386,15 +386,16 @@ struct cop_ctx {
     };
     std::vector<Retired> retired;
     LookupStage lookup_stage[2];       // cop_lookup_bulk_host, cop_lookup_audit (allocated at first use)
-    // the side calls (cop_tx_gather, cop_sketch_*, cop_aead_*, cop_fwd_*): per lane the event that
+    // the side calls (cop_tx_gather, cop_sketch_*, cop_aead_*, cop_fwd_*, cop_acl_*): per lane the event that
     // orders a call behind the lane, and per kind and lane the kernels' scratch (side_scratch:
     // allocated at the lane's first call of the kind, at the context's worst case): the gather's
     // IMIX chunk byte sums, the police's and the forward step's chunk records, the MAC waves' counts
     hipEvent_t tx_ev[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    enum { SIDE_TX_SUMS, SIDE_POLICE, SIDE_AEAD, SIDE_FWD, SIDE_KINDS };
+    enum { SIDE_TX_SUMS, SIDE_POLICE, SIDE_AEAD, SIDE_FWD, SIDE_ACL, SIDE_KINDS };
     uint32_t *side_scratch[SIDE_KINDS][MAX_LANES] = {};
     std::vector<cop_sketch *> sketches;   // cop_sketch_*: the context's sketches
     std::vector<cop_neigh *> neighs;      // cop_neigh_* / cop_fwd_*: its neighbour tables
+    std::vector<cop_acl *> acls;          // cop_acl_*: its ACLs
     hipStream_t tele_stream = nullptr;  // cop_counters_snapshot
     uint64_t *tele_host = nullptr;
     unsigned long long *tele_dev = nullptr;   // exchange_words scratch
@@ -513,6 +514,7 @@ static void coll_destroy(cop_ctx *c);
 
 static void sketch_free_all(cop_ctx *c);
 static void neigh_free_all(cop_ctx *c);
+static void acl_free_all(cop_ctx *c);
 
 void cop_destroy(cop_ctx *c)
 {
@@ -590,6 +592,7 @@ void cop_destroy(cop_ctx *c)
         if (e) (void)hipEventDestroy(e);
     sketch_free_all(c);
     neigh_free_all(c);
+    acl_free_all(c);
     free_retired(c);
     if (c->paint_h) (void)hipHostFree(c->paint_h);
     if (c->paint_d) (void)hipFree(c->paint_d);
@@ -3851,7 +3854,7 @@ int cop_lookup_audit(cop_ctx *c, uint32_t stage, const cop_lpm_table *tab, cop_a
     return rc;
 }
 
-// ---- side calls: what cop_tx_gather, cop_sketch_*, cop_aead_* and cop_fwd_* share ----
+// ---- side calls: what cop_tx_gather, cop_sketch_*, cop_aead_*, cop_fwd_* and cop_acl_* share ----
 // Their launch parameters are kernel arguments, so nothing the host could
 // rewrite under queued work. Ordering (side_run): the next launch lane, behind
 // every busy lane by events; beside a poll-mode kernel pause, run on the side
@@ -4512,6 +4515,257 @@ int cop_fwd_rewrite(cop_ctx *c, const cop_neigh *g, const cop_fwd_config *cfg, c
         l.slot_bytes = tx[i].slot_bytes;
         l.cap_bytes = (uint32_t)o.cap_bytes;
         l.cap_frames = o.cap_frames;
+    });
+}
+
+// ---- ACL (cop_acl.hip) --------------------------------------------------------
+// An ACL is a built image (acl.c) in device memory, where its parts lie, and,
+// with COP_ACL_COUNTERS, one u64 per rule. cop_acl_classify turns every batch
+// with packets into one CopKAclBatch, cop_acl_filter every forward list into
+// one CopKAclList; a launch carries up to COPK_ACL_MAXB / COPK_ACL_MAXL of
+// them with the image's description, all as kernel arguments. Ordering is
+// side_run's. cop_acl_set waits for the lanes first, so no queued launch reads
+// an image it frees or overwrites. The lane's scratch holds
+// COPK_ACL_SCRATCH_WORDS words per chunk at the worst case the context admits.
+struct cop_acl {
+    cop_ctx *owner;
+    uint32_t *image;
+    size_t image_cap;                // bytes allocated
+    unsigned long long *counters;    // or null
+    size_t counters_cap;             // words allocated
+    bool counted;
+    bool ready;                      // the last upload completed: lay describes what image holds
+    cop_acl_layout lay;
+};
+
+static void acl_free_all(cop_ctx *c)
+{
+    for (cop_acl *a : c->acls) {
+        if (a->image) (void)hipFree(a->image);
+        if (a->counters) (void)hipFree(a->counters);
+        delete a;
+    }
+    c->acls.clear();
+}
+
+static int acl_of(cop_ctx *c, const cop_acl *a, const char *what)
+{
+    return devobj_of(c, c->acls, a, what, "ACL");
+}
+
+// ... and one whose last upload completed (a cop_acl_set that failed leaves the ACL to cop_acl_set and _destroy alone)
+static int acl_ready(cop_ctx *c, const cop_acl *a, const char *what)
+{
+    if (int rc = acl_of(c, a, what)) return rc;
+    return a->ready ? 0 : set_err(c, -EINVAL, "%s: the ACL's last upload failed (cop_acl_set it again)", what);
+}
+
+// The table's image into the ACL's memory, grown if it must be, and its counters zeroed; the caller
+// has waited for whatever may use either. Runs paused, on c->stream, and completes. The layout is
+// taken over once the copy has completed; until then, and after a failure, the ACL is not ready.
+static int acl_upload(cop_ctx *c, cop_acl *a, const cop_acl_table *t, const char *what)
+{
+    char fail[64];
+    snprintf(fail, sizeof(fail), "%s: copy failed", what);
+    a->ready = false;
+    const int rc = paused_op(c, fail, [&]() -> int {
+        const size_t bytes = (size_t)t->lay.words * 4, ctr_words = t->lay.n_rules ? t->lay.n_rules : 1u;
+        if (bytes > a->image_cap) {
+            if (a->image) (void)hipFree(a->image);
+            a->image = nullptr;
+            a->image_cap = 0;
+            if (hipMalloc(&a->image, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                a->image = nullptr;
+                return set_err(c, -ENOMEM, "%s: %llu image bytes", what, (unsigned long long)bytes);
+            }
+            a->image_cap = bytes;
+        }
+        if (a->counted && ctr_words > a->counters_cap) {
+            if (a->counters) (void)hipFree(a->counters);
+            a->counters = nullptr;
+            a->counters_cap = 0;
+            if (hipMalloc(&a->counters, ctr_words * 8) != hipSuccess) {
+                (void)hipGetLastError();
+                a->counters = nullptr;
+                return set_err(c, -ENOMEM, "%s: %llu counter bytes", what, (unsigned long long)ctr_words * 8);
+            }
+            a->counters_cap = ctr_words;
+        }
+        if (hipMemcpyAsync(a->image, t->image, bytes, hipMemcpyHostToDevice, c->stream) != hipSuccess)
+            return set_err(c, -EIO, "%s", fail);
+        if (a->counters && hipMemsetAsync(a->counters, 0, a->counters_cap * 8, c->stream) != hipSuccess)
+            return set_err(c, -EIO, "%s: zeroing the counters", what);
+        return 0;
+    });
+    if (rc) return rc;
+    a->lay = t->lay;
+    a->ready = true;
+    return 0;
+}
+
+// both allocations of an ACL; inside a pause: hipFree synchronises the device and must not wait for a poll-mode kernel
+static void acl_free_mem(cop_acl *a)
+{
+    if (a->image) (void)hipFree(a->image);
+    if (a->counters) (void)hipFree(a->counters);
+    a->image = nullptr;
+    a->counters = nullptr;
+}
+
+int cop_acl_create(cop_ctx *c, const cop_acl_table *t, uint32_t flags, cop_acl **out)
+{
+    if (!c || !out) return -EINVAL;
+    if (!t) return set_err(c, -EINVAL, "acl_create: null table");
+    if (flags & ~COP_ACL_COUNTERS) return set_err(c, -EINVAL, "acl_create: unknown flags 0x%x", flags);
+    HIPCHK(c, hipSetDevice(c->device));
+    cop_acl *a = new cop_acl();
+    a->owner = c;
+    a->counted = (flags & COP_ACL_COUNTERS) != 0;
+    if (int rc = acl_upload(c, a, t, "acl_create")) {
+        (void)paused(c, [&]() -> int {
+            acl_free_mem(a);
+            return 0;
+        });
+        delete a;
+        return rc;
+    }
+    c->acls.push_back(a);
+    *out = a;
+    return 0;
+}
+
+int cop_acl_set(cop_ctx *c, cop_acl *a, const cop_acl_table *t)
+{
+    if (!c) return -EINVAL;
+    if (int rc = acl_of(c, a, "acl_set")) return rc;
+    if (!t) return set_err(c, -EINVAL, "acl_set: null table");
+    if (int rc = sync_lanes(c)) return rc;   // queued work may read the image and add to the counters
+    return acl_upload(c, a, t, "acl_set");
+}
+
+int cop_acl_destroy(cop_ctx *c, cop_acl *a)
+{
+    if (!c) return -EINVAL;
+    if (int rc = acl_of(c, a, "acl_destroy")) return rc;
+    // mem() runs inside devobj_destroy's pause: the counters go there too, the image is what it frees
+    return devobj_destroy(c, c->acls, a, "acl_destroy", "ACL", [](cop_acl *x) {
+        if (x->counters) (void)hipFree(x->counters);
+        x->counters = nullptr;
+        return x->image;
+    });
+}
+
+int cop_acl_counters_read(cop_ctx *c, cop_acl *a, uint64_t *out, uint32_t cap, int reset)
+{
+    if (!c || (cap && !out)) return -EINVAL;
+    if (int rc = acl_ready(c, a, "acl_counters_read")) return rc;
+    if (!a->counters) return set_err(c, -EINVAL, "acl_counters_read: the ACL was created without COP_ACL_COUNTERS");
+    if (int rc = sync_lanes(c)) return rc;
+    const uint32_t n = a->lay.n_rules, k = cap < n ? cap : n;
+    const char *fail = "acl_counters_read: copy failed";
+    const int rc = paused_op(c, fail, [&]() -> int {
+        if (k && hipMemcpyAsync(out, a->counters, (size_t)k * 8, hipMemcpyDeviceToHost, c->stream) != hipSuccess)
+            return set_err(c, -EIO, "%s", fail);
+        if (reset && n && hipMemsetAsync(a->counters, 0, (size_t)n * 8, c->stream) != hipSuccess)
+            return set_err(c, -EIO, "acl_counters_read: zeroing the counters");
+        return 0;
+    });
+    return rc ? rc : (int)n;
+}
+
+int cop_acl_device_ptr(cop_ctx *c, const cop_acl *a, void **image, uint64_t *image_bytes, void **counters,
+                       uint32_t *n_rules)
+{
+    if (!c) return -EINVAL;
+    if (int rc = acl_ready(c, a, "acl_device_ptr")) return rc;
+    if (!image || !image_bytes || !counters || !n_rules) return set_err(c, -EINVAL, "acl_device_ptr: null pointer");
+    *image = a->image;
+    *image_bytes = (uint64_t)a->lay.words * 4;
+    *counters = a->counters;
+    *n_rules = a->lay.n_rules;
+    return 0;
+}
+
+static void acl_tab(CopKAclTab &k, const cop_acl *a, bool counters)
+{
+    k.image = a->image;
+    k.counters = counters ? a->counters : nullptr;
+    k.n_rules = a->lay.n_rules;
+    k.row_words = a->lay.row_words;
+    for (int f = 0; f < 4; f++) {
+        k.niv[f] = a->lay.niv[f];
+        k.off_starts[f] = a->lay.off_starts[f];
+        k.off_rows[f] = a->lay.off_rows[f];
+    }
+    k.off_proto = a->lay.off_proto;
+    k.off_rank = a->lay.off_rank;
+}
+
+int cop_acl_classify(cop_ctx *c, const cop_acl *a, const cop_batch *batches, const cop_acl_desc *descs, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (int rc = acl_ready(c, a, "acl_classify")) return rc;
+    if (nb == 0) return 0;
+    if (nb > c->cfg.max_batches) return set_err(c, -EINVAL, "acl_classify: nb %u > max_batches", nb);
+    const char *why = "";
+    if (int rc = cop_acl_validate(a->image, (uint64_t)a->lay.words * 4, a->counters, a->lay.n_rules, batches, descs, nb, 0,
+                                  1, 0, c->cfg.max_batch, &why))
+        return set_err(c, rc, "acl_classify: %s", why);
+    return side_run(c, "acl_classify", [&](int, hipStream_t s) -> int {
+        CopKAclWords p;
+        memset(&p, 0, sizeof(p));
+        acl_tab(p.tab, a, false);
+        auto flush = [&]() -> int {
+            const hipError_t e = copk_acl_words_launch(&p, s);
+            p.nb = 0;
+            p.nchunks = 0;
+            return e == hipSuccess ? 0 : set_err(c, -EIO, "acl_classify launch: %s", hipGetErrorString(e));
+        };
+        for (uint32_t i = 0; i < nb; i++) {
+            const cop_batch &b = batches[i];
+            if (!b.n) continue;
+            if (p.nb == COPK_ACL_MAXB)
+                if (int rc = flush()) return rc;
+            CopKAclBatch &k = p.b[p.nb++];
+            k.pkts = (const uint8_t *)b.pkts + b.data_off;
+            k.offsets = b.offsets;
+            k.words = descs[i].words;
+            k.n = b.n;
+            k.stride = b.stride;
+            k.chunk_begin = p.nchunks;
+            p.nchunks += (b.n + COPK_ACL_CHUNK - 1) / COPK_ACL_CHUNK;
+        }
+        return flush();
+    });
+}
+
+int cop_acl_filter(cop_ctx *c, const cop_acl *a, const cop_batch *batches, const cop_acl_desc *descs, uint32_t nb)
+{
+    if (!c) return -EINVAL;
+    if (int rc = acl_ready(c, a, "acl_filter")) return rc;
+    if (nb == 0) return 0;
+    uint32_t n_lists = 1;
+    int seg = 0;
+    if (int rc = list_call_check(c, "acl_filter", nb, &n_lists, &seg, [&](uint32_t nl, int sg, const char **why) {
+            return cop_acl_validate(a->image, (uint64_t)a->lay.words * 4, a->counters, a->lay.n_rules, batches, descs, nb,
+                                    1, nl, sg, c->cfg.max_batch, why);
+        }))
+        return rc;
+    return side_run(c, "acl_filter", [&](int lane, hipStream_t s) -> int {
+        CopKAcl p;
+        memset(&p, 0, sizeof(p));
+        acl_tab(p.tab, a, true);
+        p.seg = seg ? 1u : 0u;
+        if (int rc = side_scratch(c, cop_ctx::SIDE_ACL, lane, chunk_scratch_bytes(c, n_lists, COPK_ACL_SCRATCH_WORDS),
+                                  &p.scratch))
+            return rc;
+        return pack_lists(c, "acl_filter", p, COPK_ACL_MAXL, copk_acl_filter_launch, s, batches, nb, n_lists,
+                          [&](CopKAclList &l, uint32_t i, uint32_t q) {
+                              l.out_idx = descs[i].out_idx + (size_t)q * batches[i].n;
+                              l.out_count = descs[i].out_count + q;
+                              l.status = descs[i].status + 4 * q;
+                          });
     });
 }
 

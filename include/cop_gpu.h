@@ -1064,6 +1064,147 @@ int  cop_fwd_rewrite_host(const cop_neigh_entry *entries, uint32_t n_entries, co
                           uint32_t n_lists, int seg, uint32_t max_batch);
 uint16_t cop_ipv4_csum_host(const uint8_t hdr[20]);
 
+/* ------------------------------------------------------------------------ */
+/* ACL: 5-tuple classify and filter of batches on the device                */
+/* ------------------------------------------------------------------------ */
+
+/* A priority-ordered rule list over (source prefix, destination prefix,
+ * protocol, source-port range, destination-port range): what the firewall
+ * stage, one longest-prefix match on the source, cannot say ("drop TCP to
+ * port 22 unless it comes from 10.1.0.0/16"). cop_acl_classify gives every
+ * packet of a batch its word; cop_acl_filter, a side call of
+ * cop_sketch_police's shape, removes from a batch's forward lists the entries
+ * whose rule drops. The chain cop_submit -> cop_acl_filter -> cop_fwd_check
+ * -> cop_tx_gather needs no sync. This is not rte_acl: the semantics are the
+ * ones written here, and their ground truth is a linear scan of the rules.
+ *
+ * Key of a packet, from the bytes b[] where cop_batch puts it (48 readable
+ * bytes; none past 37 is read). The word is exactly COP_ACL_SKIP, and nothing
+ * past byte 15 is used, when b[12..13] != 08 00, b[14] >> 4 != 4 (the
+ * pipeline's two checks) or (b[14] & 15) < 5. Otherwise proto = b[23],
+ * src = BE32(b[26..29]), dst = BE32(b[30..33]); with (b[14] & 15) == 5 and a
+ * fragment offset ((b[20] & 0x1F) << 8 | b[21]) of 0, sport = BE16(b[34..35])
+ * and dport = BE16(b[36..37]) whatever the protocol; in every other case
+ * (options, a later fragment) sport = dport = 0. MF alone (b[20] & 0x20, offset
+ * 0) is a first fragment and has ports.
+ *
+ * Word of a key: a rule matches iff src and dst lie in its prefixes (depth 0:
+ * any), (proto & proto_mask) == (rule.proto & proto_mask), and both ports lie
+ * in its inclusive ranges. The winner is the matching rule of highest
+ * priority, equal priorities the lowest index; the word is
+ * index | COP_ACL_HIT | (action ? COP_ACL_DROP : 0), index the rule's position
+ * in the array given to cop_acl_build. No match: exactly 0. */
+#define COP_ACL_MAX_RULES 1024u
+#define COP_ACL_HIT   0x01000000u   /* same bit as COP_LOOKUP_HIT */
+#define COP_ACL_DROP  0x04000000u   /* same bit as COP_LOOKUP_DROP: the matching rule's action != 0 */
+#define COP_ACL_SKIP  0x08000000u   /* not classified: not IPv4 by the pipeline's two checks, or IHL < 5 */
+#define COP_ACL_COUNTERS 0x1u       /* cop_acl_create flag: one u64 hit counter per rule */
+
+typedef struct cop_acl_rule {          /* 28 bytes */
+    uint32_t src_ip, dst_ip;           /* host byte order, unmasked accepted (masked to the depth) */
+    uint16_t sport_lo, sport_hi;       /* inclusive; lo > hi is -EINVAL */
+    uint16_t dport_lo, dport_hi;
+    uint8_t  src_depth, dst_depth;     /* 0..32, 0 = any address */
+    uint8_t  proto, proto_mask;        /* matches iff (p & proto_mask) == (proto & proto_mask); mask 0 = any */
+    int32_t  priority;                 /* the higher wins; equal priorities: the lower rule index wins */
+    uint32_t action;                   /* 0 permit, non-zero drop (the firewall's convention) */
+} cop_acl_rule;
+typedef struct cop_acl_key { uint32_t src, dst; uint16_t sport, dport; uint8_t proto, _pad[3]; } cop_acl_key;
+
+/* The built image, a bit-vector classifier: rules ranked by
+ * (priority descending, index ascending), rank p bit p of a row of row_words
+ * u32; per range field the sorted interval starts and one row per interval,
+ * 256 rows for the protocol, and the rank -> word table. */
+typedef struct cop_acl_report {
+    uint32_t n_rules;
+    uint32_t n_intervals[4];   /* src, dst, sport, dport */
+    uint32_t row_words;        /* 4 * ceil(max(n, 1) / 128) */
+    uint32_t first_error_idx;  /* the first bad rule (-EINVAL), n (-ENOSPC), else 0xFFFFFFFF */
+    uint32_t _pad;
+    uint64_t image_bytes;
+} cop_acl_report;
+typedef struct cop_acl_table cop_acl_table;   /* host object, no GPU needed (as cop_lpm_table) */
+typedef struct cop_acl cop_acl;               /* device object, owned by one context; several may exist */
+
+/* n may be 0 (rules may then be NULL): every key misses. rep may be NULL.
+ * -EINVAL: a depth above 32, lo > hi (rep->first_error_idx the rule); -ENOSPC:
+ * n > COP_ACL_MAX_RULES; -ENOMEM. Nothing is built on an error. */
+int  cop_acl_build(const cop_acl_rule *rules, uint32_t n, cop_acl_table **out, cop_acl_report *rep);
+void cop_acl_free(cop_acl_table *t);
+/* out[i] = the word of keys[i], from the built image. */
+int  cop_acl_match_host(const cop_acl_table *t, const cop_acl_key *keys, uint32_t n, uint32_t *out);
+
+/* Uploads the image, synchronously; with COP_ACL_COUNTERS also allocates and
+ * zeroes one u64 per rule. -EINVAL: unknown flags. */
+int  cop_acl_create(cop_ctx *ctx, const cop_acl_table *t, uint32_t flags, cop_acl **out);
+/* Waits for the context's queued work, then uploads another table's image
+ * (the allocations grow if they must) and zeroes the counters. Synchronous.
+ * If it fails (-ENOMEM, -EIO) the ACL holds no usable image: every call on it
+ * but cop_acl_set and cop_acl_destroy is -EINVAL until a set succeeds. */
+int  cop_acl_set(cop_ctx *ctx, cop_acl *acl, const cop_acl_table *t);
+/* Waits for the context's queued work, then frees. cop_destroy frees the ACLs
+ * that are left. */
+int  cop_acl_destroy(cop_ctx *ctx, cop_acl *acl);
+/* cop_rule_counters_read's contract: waits for the context's queued work,
+ * copies min(cap, n_rules) words (word i: rule index i), returns n_rules (or
+ * -errno); reset != 0 zeroes them after the copy. -EINVAL without
+ * COP_ACL_COUNTERS. All four calls pause a poll-mode kernel, as cop_neigh_set
+ * does. */
+int  cop_acl_counters_read(cop_ctx *ctx, cop_acl *acl, uint64_t *out, uint32_t cap, int reset);
+/* The image and the counters in device memory (counters NULL without
+ * COP_ACL_COUNTERS; n_rules words, for a caller's own element-wise sum across
+ * GPUs). Valid until the next cop_acl_set or cop_acl_destroy of the ACL. */
+int  cop_acl_device_ptr(cop_ctx *ctx, const cop_acl *acl, void **image, uint64_t *image_bytes, void **counters,
+                        uint32_t *n_rules);
+
+/* One per batch. classify reads words; filter reads the other three. */
+typedef struct cop_acl_desc {
+    uint32_t *words;      /* device, n u32: classify's output */
+    uint32_t *out_idx;    /* device; the layout and capacity of the batch's fwd_idx on this context */
+    uint32_t *out_count;  /* device; the layout of fwd_count */
+    uint32_t *status;     /* device, 16-byte aligned; 4 words per forward list: kept, removed, kept as miss, kept as skip */
+} cop_acl_desc;
+
+/* Both calls are ordered as cop_sketch_police is: asynchronous on the next
+ * launch lane behind every lane's queued work, outputs valid after cop_sync;
+ * synchronous beside a poll-mode kernel. nb == 0 returns 0.
+ *
+ * classify: words[i] = the word of packet i, for every packet of the batch.
+ * Of a cop_batch only pkts, offsets, n, stride and data_off are read. Nothing
+ * else is written; no counter is touched.
+ *
+ * filter: the context's forward lists walked with the gather's clamps (dense;
+ * per vport with COP_CFG_DEMUX_PORTS; segments with COP_CFG_SEG_LISTS; an
+ * entry >= n is read as n - 1, a length clamped to what the layout holds). An
+ * entry is kept iff its packet's word lacks COP_ACL_DROP: misses and skipped
+ * packets are kept (default deny is a depth-0 catch-all rule of lowest
+ * priority). Kept entries are written as read, in list order, to out_idx /
+ * out_count of the same layout, which cop_tx_gather and cop_fwd_check take as
+ * they are; status[4q ..] = {kept, removed, kept as miss, kept as skip}, one
+ * status per batch for segmented lists. With COP_ACL_COUNTERS every list
+ * entry whose word has COP_ACL_HIT adds 1 to its rule's counter, kept or
+ * removed; nothing else adds. Nothing of out_idx is written past a kept count;
+ * the batch, its lists and its records are not written. A batch with n == 0
+ * is skipped whole.
+ *
+ * -EINVAL (nothing launched, nothing written): an ACL of another context;
+ * nb > max_batches; n > max_batch; n > 0 with a needed pointer NULL; packet
+ * starts not 16-byte aligned; a slot batch's stride below 48; words, out_idx
+ * or out_count not 4-byte aligned; in the filter a COP_CFG_NO_COMPACT context
+ * and status not 16-byte aligned; any overlap of an extent the call writes
+ * with any other extent of the call, the ACL's image or its counters. */
+int  cop_acl_classify(cop_ctx *ctx, const cop_acl *acl, const cop_batch *batches, const cop_acl_desc *descs,
+                      uint32_t nb);
+int  cop_acl_filter(cop_ctx *ctx, const cop_acl *acl, const cop_batch *batches, const cop_acl_desc *descs,
+                    uint32_t nb);
+/* The host mirror (csrc/acl.c; no GPU needed): the same over host memory.
+ * counters: n_rules u64 words or NULL (none counted). The list layout is
+ * explicit, as cop_sketch_police_host takes it; max_batch 0 for no limit. */
+int  cop_acl_classify_host(const cop_acl_table *t, const cop_batch *batches, const cop_acl_desc *descs, uint32_t nb,
+                           uint32_t max_batch);
+int  cop_acl_filter_host(const cop_acl_table *t, uint64_t *counters, const cop_batch *batches,
+                         const cop_acl_desc *descs, uint32_t nb, uint32_t n_lists, int seg, uint32_t max_batch);
+
 /* End-to-end path from host memory (NIC/KNI mbuf data): gather the first 64
  * bytes of each packet into pinned staging, hipMemcpyAsync H2D, run the
  * pipeline, hipMemcpyAsync D2H of results and forward list. Synchronous. */
