@@ -950,6 +950,23 @@ class Context:
         _check(rc, self, "launch_forms")
         return self.LAUNCH_FORMS[int(out[0])], self.LAUNCH_FORMS[int(out[1])], int(out[2])
 
+    LAUNCH_LAYOUTS = {0: "slots", 1: "imix", 2: "coalesced", 3: "hdr16"}
+
+    def launch_plan(self):
+        """(packet layout, packets per lane) of the same launch
+        (cop_debug_launch_plan): slots = per-lane slot loads, imix,
+        coalesced, hdr16 = packed 16- or 12-byte records; None before any
+        launch."""
+        f = lib().cop_debug_launch_plan
+        f.restype = c_int
+        f.argtypes = [c_void_p, c_void_p]
+        out = np.zeros(2, dtype=np.uint32)
+        rc = f(self.handle, _ptr(out))
+        if rc == -errno.ENOENT:
+            return None
+        _check(rc, self, "launch_plan")
+        return self.LAUNCH_LAYOUTS[int(out[0])], int(out[1])
+
     def lookup_form(self, stage: int) -> str:
         """The table form lookup_bulk uses for a stage now (ROUTE_FORMS names;
         "dir-packed": DIR-24-8 with packed tbl8 groups)."""

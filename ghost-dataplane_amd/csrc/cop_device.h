@@ -462,22 +462,27 @@ __device__ __forceinline__ void load_step(const StepGeom &g, const uint8_t *pk0,
 // line, where per-lane loads (a dwordx4 at byte 12 across a 16-byte
 // boundary and a dwordx2 at 28) touch 64 lines per instruction, twice.
 // Packet starts are 16-byte aligned and hold 48 readable bytes
-// (include/cop_gpu.h, cop_batch).
+// (include/cop_gpu.h, cop_batch). offsets[i] and data_off are independent
+// u32 values whose sum may pass 2^32: the plain loads add the lane's 32-bit
+// offset + chunk (offsets[i] <= 2^32 - 64, cop_batch) to the wave-uniform
+// 64-bit base pkts + data_off. The coherent loads take 31-bit offsets from
+// pkts (cop_pmd_start checks the slots' span).
 __device__ __forceinline__ void load_step_imix(const StepGeom &g, const uint8_t *pkts, uint32_t off,
                                                uint32_t data_off, u32x4 (&v)[3], bool sys = false)
 {
     uint32_t o[3];
 #pragma unroll
     for (int c = 0; c < 3; c++)
-        o[c] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(g.lpk[c] << 2), (int)off) + data_off + g.lch[c];
+        o[c] = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(g.lpk[c] << 2), (int)off) + g.lch[c];
     if (sys) {
         const __amdgpu_buffer_rsrc_t rs = sys_rsrc(pkts);
 #pragma unroll
-        for (int c = 0; c < 3; c++) v[c] = ld_sys16(rs, o[c]);
+        for (int c = 0; c < 3; c++) v[c] = ld_sys16(rs, o[c] + data_off);
         return;
     }
+    const uint8_t *base = pkts + data_off;
 #pragma unroll
-    for (int c = 0; c < 3; c++) v[c] = __builtin_nontemporal_load((const u32x4 *)(pkts + o[c]));
+    for (int c = 0; c < 3; c++) v[c] = __builtin_nontemporal_load((const u32x4 *)(base + o[c]));
 }
 
 // the offset of the step's packet pb + lane (clamped to `last`)

@@ -224,6 +224,11 @@ int cop_debug_lookup_form(cop_ctx *c, uint32_t stage);
  * none). cop_debug_pmd_forms: the same of a poll-mode kernel. */
 int cop_debug_launch_forms(cop_ctx *c, uint32_t out[3]);
 int cop_debug_pmd_forms(const cop_pmd *m, uint32_t out[3]);
+/* tests: the rest of that launch's kernel instantiation: out[0] the packet
+ * layout (COPK_LAY_*: 0 per-lane slot loads, 1 IMIX, 2 coalesced slots,
+ * 3 packed 16- or 12-byte records), out[1] the packets per lane (1, 4 or 8;
+ * the tile is 256 times that). -ENOENT as above. */
+int cop_debug_launch_plan(cop_ctx *c, uint32_t out[2]);
 
 /* ---- bulk lookups (lpm_lookup.c) ---------------------------------------- */
 /* What a lookup word keeps of a device entry whose hit bit is set: an NH

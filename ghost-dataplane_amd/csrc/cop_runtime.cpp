@@ -304,6 +304,7 @@ struct cop_ctx {
     // cop_debug_launch_forms: what fill_launch chose for the most recent one-shot launch
     bool last_valid = false;
     uint32_t last_fw_mode = 0, last_lpm_mode = 0, last_lds_bytes = 0;
+    uint32_t last_layout = 0, last_ppt = 0;   // cop_debug_launch_plan
     char err[256] = {0};
 
     uint32_t *rt_top = nullptr;
@@ -1110,6 +1111,17 @@ int cop_debug_launch_forms(cop_ctx *c, uint32_t out[3])
     return 0;
 }
 
+// tests: the packet layout (COPK_LAY_*) and the packets per lane of the same launch: with the
+// forms, the kernel instantiation that ran
+int cop_debug_launch_plan(cop_ctx *c, uint32_t out[2])
+{
+    if (!c || !out) return -EINVAL;
+    if (!c->last_valid) return -ENOENT;
+    out[0] = c->last_layout;
+    out[1] = c->last_ppt;
+    return 0;
+}
+
 static void harvest_one(cop_ctx *c, Lane &L)
 {
     int idx = (L.ev_head - L.ev_count + TIMING_SLOTS) % TIMING_SLOTS;
@@ -1379,6 +1391,8 @@ static int launch_on(cop_ctx *c, Lane &L, CopKParams &p, bool imix, Plan pl, uin
     c->last_fw_mode = (uint32_t)fw_mode;
     c->last_lpm_mode = (uint32_t)lpm_mode;
     c->last_lds_bytes = lds_bytes;
+    c->last_layout = (uint32_t)pl.layout;
+    c->last_ppt = (uint32_t)ppt;
     hipError_t e = copk_launch(&p, fw_mode, lpm_mode, pl.layout, ppt, grid, lds_bytes, L.s);
     if (e != hipSuccess) return set_err(c, -EIO, "launch: %s", hipGetErrorString(e));
     if (p.hit_region && (e = copk_hit_count(&p, grid, COPK_BLOCK * (uint32_t)ppt, L.s)) != hipSuccess)

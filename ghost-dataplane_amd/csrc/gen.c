@@ -195,7 +195,7 @@ int cop_gen_imix(uint64_t seed, uint32_t n, const cop_trace_opts *opts, const co
         uint32_t r = rnd(&ss, 12);
         uint32_t len = r < 7 ? 64u : (r < 11 ? 594u : 1518u);
         if (slab) {
-            if (off > 0xFFFFFFFFull) return -ERANGE;
+            if (off > 0xFFFFFFFFull - 63u) return -ERANGE;   /* cop_batch: offsets[i] <= 2^32 - 64 */
             offsets[i] = (uint32_t)off;
             make_frame(&s, opts, fw, n_fw, routes, n_routes, slab + off, len);
         }

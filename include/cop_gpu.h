@@ -528,7 +528,9 @@ void cop_pack_headers12(const void *const *pkt_data, uint32_t n, uint8_t *out /*
  * Every packet start must be 16-byte aligned and hold >= 48 readable bytes
  * (the fields sit at fixed offsets 12..33, as firewall.c:143-145 /
  * switch.c:125-127 read them; the streaming kernel moves whole 16-byte
- * chunks, and any Ethernet frame has >= 60). Outputs: results[i] for every packet;
+ * chunks, and any Ethernet frame has >= 60). offsets[i] and data_off are
+ * independent: their sum may pass 2^32 (the address is formed in 64 bits);
+ * offsets[i] itself must be <= 2^32 - 64. Outputs: results[i] for every packet;
  * fwd_idx[0..*fwd_count) = indices of FORWARD packets in arrival order (the
  * order coprocessor() enqueues them to tx_q, switch.c:464-470). */
 typedef struct cop_batch {

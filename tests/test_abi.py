@@ -43,6 +43,24 @@ def test_every_declared_symbol_is_exported():
     assert declared_functions() <= set(cg.SIGNATURES), declared_functions() - set(cg.SIGNATURES)
 
 
+def test_debug_accessors_are_exported():
+    """The test accessors of csrc/cop_internal.h that the binding looks up by
+    name (Context.launch_forms, launch_plan, route_form) are exported, and
+    fail cleanly without a context."""
+    out = subprocess.run(["nm", "-D", "--defined-only", cg.LIB_PATH], capture_output=True, text=True,
+                         check=True).stdout
+    exported = {line.split()[-1] for line in out.splitlines() if " T " in line}
+    internal = open(os.path.join(ROOT, "ghost-dataplane_amd", "csrc", "cop_internal.h")).read()
+    for f in ("cop_debug_launch_forms", "cop_debug_launch_plan", "cop_debug_route_form"):
+        assert f in exported, f
+        assert re.search(rf"\bint {f}\(", internal), f
+    plan = cg.lib().cop_debug_launch_plan
+    plan.restype = ctypes.c_int
+    plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    two = (ctypes.c_uint32 * 2)()
+    assert plan(None, two) == -22 and plan(None, None) == -22   # -EINVAL
+
+
 def test_header_is_plain_c():
     text = re.sub(r"/\*.*?\*/", "", open(HDR).read(), flags=re.S)
     for bad in ("hip_runtime", "cuda", "torch", "hipStream_t", "__global__", "#ifdef __HIP"):
